@@ -11,11 +11,20 @@ problem ranges, so scaling is weak.
 Output: one JSON line on rank 0 (driver contract), including
   roofline     — FP64 work of the solver kernel (SURVEY.md §8(d) formula,
                  939.3 KFLOP per problem-iteration at C2) over its HIP-event
-                 duration on the solver's own stream, against the 78.6 TFLOP/s
-                 FP64 peak;
+                 duration on the solver's own stream (the timed steps' own
+                 launches), against the 78.6 TFLOP/s FP64 peak.
+A plain run does only that: set-up, W warm-up steps, the K timed steps, the
+line.  `--full` adds the measurements that take runs of their own (N=1):
+  ingest, explicit_inverse, rank_update_plugin — the PCIe-inclusive rate, the
+                 other operation order and the rank-update plugin on the same
+                 batch (`--no-ingest` drops them);
   cpu_baseline — the CPU oracle (reference op order, oracle/) on a bounded
-                 sample of the same problems on this host's cores.
-Launch: python bench.py [--gpus N --steps K --warmup W]
+                 sample of the same problems on this host's cores, and its
+                 structured and all-cores forms (`--no-cpu` drops them).
+`--dump-outputs DIR` writes what the last timed step returned (x, y, z, s,
+iters, status[, res]) as DIR/<name>.npy, float64: every problem, or a fixed
+seeded sample of them (DIR/sample_index.npy) where the whole exceeds 64 MB.
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
         N>1 with no launcher: bench.py starts the N ranks itself under
         torch.distributed.run (from a parent that never touches the GPU);
         under a launcher (WORLD_SIZE set) WORLD_SIZE must equal N.
@@ -311,6 +320,8 @@ def sqr_bench(args, emit=True):
     ctx.sync()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, B, skip=() if m else ("cy",))  # the last timed solve_kkt's result
     for _ in range(2):
         step(True)  # per-kernel HIP-event durations, outside the timed region
     ms_setup = sum(t_setup) / len(t_setup)
@@ -366,7 +377,7 @@ def sqr_bench(args, emit=True):
                      "solve_TFLOPs": fv * B / (ms_solve * 1e-3) / 1e12,
                      "bytes_per_problem": {"setup": bs, "solve": bv}, "flops_per_problem": {"setup": fs, "solve": fv}},
     }
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         sys.path.insert(0, os.path.join(HERE, "oracle"))
         import oracle as O  # test infrastructure: the CPU line only
         import numpy as np
@@ -391,6 +402,38 @@ def sqr_bench(args, emit=True):
     if emit:
         print(json.dumps(line), flush=True)
     return line
+
+
+SIDE_STEPS_MAX = 20  # --full: repetitions of each side measurement (a C2 ingest batch is 3.9 GB of input)
+DUMP_BUDGET_BYTES = 48 << 20  # of the 64 MB a dump may hold
+DUMP_SAMPLE_SEED = 0x534F4350
+
+
+def dump_outputs(path, out, B, skip=()):
+    """--dump-outputs: every per-problem array of `out` (the dict the timed
+    path returned from its last step) as path/<name>.npy, float64, one row per
+    problem.  Where all B problems exceed DUMP_BUDGET_BYTES the same seeded,
+    sorted sample of problem indices is taken from every array and written
+    beside them as sample_index.npy; it depends on B and the row widths only,
+    so two builds run with the same arguments dump the same problems."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    rows = {}
+    for name, t in out.items():
+        t = torch.as_tensor(t)
+        w = t.numel() // B
+        if name not in skip and w and w * B == t.numel():
+            rows[name] = t.reshape(B, w)
+    keep = DUMP_BUDGET_BYTES // (8 * sum(t.shape[1] for t in rows.values()))
+    idx = None
+    if B > keep:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(B, size=keep, replace=False))
+        np.save(os.path.join(path, "sample_index.npy"), idx.astype(np.float64))
+    for name, t in rows.items():
+        if idx is not None:
+            t = t[torch.as_tensor(idx, device=t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(np.float64))
 
 
 def free_port():
@@ -444,11 +487,19 @@ def main(argv=None):
     ap.add_argument("--explicit-inverse", action="store_true",
                     help="SOCP_F_EXPLICIT_INVERSE: the reference's operation order (Li = H^-1 formed, "
                          "densesolver.jl:48) instead of the default H = L L' + triangular solves")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="per CPU line (two lines)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run (N=1 only) the measurements that take runs of their own: "
+                         "the PCIe-inclusive ingest line, the explicit-inverse and rank-update summaries, and the "
+                         "CPU lines; --no-ingest and --no-cpu drop their part.  Off by default: a plain run sets "
+                         "up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float64; a fixed seeded "
+                         "sample of the problems, DIR/sample_index.npy, where the whole exceeds 64 MB)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="per CPU line (two lines), with --full")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU lines")
     ap.add_argument("--no-ingest", action="store_true",
-                    help="skip the PCIe-inclusive line (host batches through socp_ingest, N=1 only) and the "
-                         "other-mode summaries (explicit inverse, rank-update plugin): only the timed solver launches")
+                    help="with --full: skip the PCIe-inclusive line (host batches through socp_ingest, N=1 only) and "
+                         "the other-mode summaries (explicit inverse, rank-update plugin)")
     ap.add_argument("--traffic-json", default=None,
                     help="PMC traffic summary (tools/pmc_traffic.py); default: the newest profiles/rNN_pmc_traffic[_<config>].json")
     ap.add_argument("--stub-solve", action="store_true", help=argparse.SUPPRESS)
@@ -539,6 +590,8 @@ def run_rank(args, world):
         kernel_ms = ctx.kernel_times(args.steps)  # the timed steps' solver launches (the last 64 at most)
         kname = ctx.last_kernel_name()
     out, dt, iters_total = tr["out"], tr["dt"], tr["iters_total"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, B, skip=() if m else ("y",))  # rank 0's own shard
     status_counts = torch.bincount(out["status"].long(), minlength=5).tolist()
 
     if rank == 0:
@@ -622,15 +675,18 @@ def run_rank(args, world):
             line["gathered"] = {"status_counts": torch.bincount(gst, minlength=5).tolist(),
                                 "iters_sum": int(tr["gathered"]["iters"].long().sum().item()),
                                 "problems": int(gst.numel())}
-        extras = world == 1 and not stub
+        # --full: the measurements that take runs of their own, after the line's own figures are
+        # fixed; each repeats at most SIDE_STEPS_MAX times however many steps were timed
+        extras = args.full and world == 1 and not stub
+        side_steps = min(args.steps, SIDE_STEPS_MAX)
         if extras and not args.no_ingest:
-            line["ingest"] = ingest_line(S, cfg, B, K, tol, (c, A, b, G, h), args.steps, ctx)
+            line["ingest"] = ingest_line(S, cfg, B, K, tol, (c, A, b, G, h), side_steps, ctx)
         if extras and not args.explicit_inverse and not ref_rule and not args.no_ingest:
             # the other operation order on the same batch (never `value`): the
             # reference's explicit Li = H^-1 (SOCP_F_EXPLICIT_INVERSE); its own
             # line is `--explicit-inverse`
             xi_ms, xo = [], None
-            for rep in range(1 + args.steps):
+            for rep in range(1 + side_steps):
                 xo = S.batch_solve(cfg.cones, n, m, k, c, A, b, G, h, sing, maxit=K, tol=tol, ctx=ctx, out=xo,
                                    explicit_inverse=True)
                 if rep:
@@ -647,8 +703,8 @@ def run_rank(args, world):
         if extras and not args.no_ingest and cfg.name == "C2" and not ref_rule:
             # the rank-update plugin (SparseSolver + SqrScaling, socp_sqr_*) at the same shape: its
             # own line is `--mode sqr`; summarised here so every default run records it
-            sq = sqr_bench(argparse.Namespace(config=cfg.name, batch=B, steps=args.steps, warmup=1, no_cpu=True,
-                                              traffic_json=None), emit=False)
+            sq = sqr_bench(argparse.Namespace(config=cfg.name, batch=B, steps=side_steps, warmup=1, no_cpu=True,
+                                              full=False, traffic_json=None, dump_outputs=None), emit=False)
             line["rank_update_plugin"] = {"value": sq["value"], "unit": sq["unit"], "ms_per_step": sq["ms_per_step"],
                                           "kernels_ms": sq["kernels"], "status_counts": sq["status_counts"],
                                           "solve_socp": sq["solve_socp"],

@@ -29,12 +29,12 @@ timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/pro
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c1 -o c1 -- python3 bench.py --config C1 --steps 5 --warmup 2 --no-cpu --no-ingest > $O/prof_c1.log 2>&1 || { tail -30 $O/prof_c1.log; exit 1; }
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_sqr -o sqr -- python3 bench.py --mode sqr --steps 3 --warmup 1 --no-cpu > $O/prof_sqr.log 2>&1 || { tail -30 $O/prof_sqr.log; exit 1; }
 echo "prof done"
-timeout -k 10 500 python3 bench.py --traffic-json $O/pmc_traffic.json > $O/bench_c2.log 2>&1 || { tail -30 $O/bench_c2.log; exit 1; }
+timeout -k 10 500 python3 bench.py --full --traffic-json $O/pmc_traffic.json > $O/bench_c2.log 2>&1 || { tail -30 $O/bench_c2.log; exit 1; }
 grep '^{' $O/bench_c2.log | cut -c1-300
 timeout -k 10 300 python3 bench.py --explicit-inverse --no-cpu --no-ingest > $O/bench_xi.log 2>&1 || { tail -30 $O/bench_xi.log; exit 1; }
-timeout -k 10 400 python3 bench.py --config C4 --steps 3 --warmup 1 --no-ingest --traffic-json $O/pmc_traffic_c4.json > $O/bench_c4.log 2>&1 || { tail -30 $O/bench_c4.log; exit 1; }
-timeout -k 10 300 python3 bench.py --config C1 --no-ingest --traffic-json $O/pmc_traffic_c1.json > $O/bench_c1.log 2>&1 || { tail -30 $O/bench_c1.log; exit 1; }
-timeout -k 10 400 python3 bench.py --mode reference --no-ingest > $O/bench_refrule.log 2>&1 || { tail -30 $O/bench_refrule.log; exit 1; }
-timeout -k 10 400 python3 bench.py --mode sqr --steps 10 --warmup 2 > $O/bench_sqr.log 2>&1 || { tail -30 $O/bench_sqr.log; exit 1; }
+timeout -k 10 400 python3 bench.py --full --config C4 --steps 3 --warmup 1 --no-ingest --traffic-json $O/pmc_traffic_c4.json > $O/bench_c4.log 2>&1 || { tail -30 $O/bench_c4.log; exit 1; }
+timeout -k 10 300 python3 bench.py --full --config C1 --no-ingest --traffic-json $O/pmc_traffic_c1.json > $O/bench_c1.log 2>&1 || { tail -30 $O/bench_c1.log; exit 1; }
+timeout -k 10 400 python3 bench.py --full --mode reference --no-ingest > $O/bench_refrule.log 2>&1 || { tail -30 $O/bench_refrule.log; exit 1; }
+timeout -k 10 400 python3 bench.py --full --mode sqr --steps 10 --warmup 2 > $O/bench_sqr.log 2>&1 || { tail -30 $O/bench_sqr.log; exit 1; }
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -30 $O/smoke.log; exit 1; }
 echo "all done"
