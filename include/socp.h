@@ -50,6 +50,8 @@ extern "C" {
 #define SOCP_CHOL_H_FAILED 2  /* H = G'W^-2G (+A'A) not positive definite (densesolver.jl:47)        */
 #define SOCP_CHOL_S_FAILED 3  /* S = A H^-1 A' not positive definite (densesolver.jl:51)            */
 #define SOCP_DOMAIN_ERROR 4   /* sqrt of a negative number: Julia throws DomainError (scalings.jl:46,47,57,68,91; mats.jl:71) */
+#define SOCP_PRIMAL_INFEASIBLE 5 /* SOCP_F_DETECT_INFEASIBLE: (y, z) certifies that no x, s in K satisfy Ax = b, Gx + s = h */
+#define SOCP_DUAL_INFEASIBLE 6   /* SOCP_F_DETECT_INFEASIBLE: (x, s) is a ray along which c'x is unbounded below            */
 
 /* ---- cone kinds (reference Socp.jl:8-16) ---- */
 #define SOCP_CONE_POC 0 /* nonnegative orthant, POC{D}(offs) */
@@ -91,6 +93,32 @@ typedef struct socp_params {
  * DESIGN.md §9).  Honoured by socp_batch_solve[_ex], socp_batch_kkt_solve,
  * socp_dense_create (for all calls of the handle) and socp_ingest_submit. */
 #define SOCP_F_EXPLICIT_INVERSE 8
+/* Infeasibility / unboundedness detection (the reference has none: solver.jl:
+ * 105-151 runs such a problem to maxit or into a PosDefException).  Bits 16 to
+ * 128 belong to flags of the CPU oracle.  With this flag the rule below is
+ * evaluated where the exit test is (solver.jl:122): at the start of iteration
+ * `it` < maxit, after compute_scaling's domain check and the exit test, before
+ * the factorisation; warm-started solves included.  tau is the context's
+ * infeasibility tolerance (socp_ctx_set_infeasibility_tol, default 1e-7).
+ *   1. hz = h'z + b'y.  If hz < 0 and ||A'y + G'z||_2 < tau (-hz):
+ *      status SOCP_PRIMAL_INFEASIBLE; y and z are returned multiplied by
+ *      1/(-hz), so that b'y + h'z = -1; x and s as they stand.
+ *   2. Otherwise cx = c'x.  If cx < 0 and max(||Ax||_2, ||Gx + s||_2) < tau (-cx):
+ *      status SOCP_DUAL_INFEASIBLE; x and s are returned multiplied by
+ *      1/(-cx), so that c'x = -1; y and z as they stand.
+ * In both cases iters = it and res[] holds the exit-test quantities at the
+ * iterate before that multiplication.  With m = 0 the b and A terms vanish.
+ * Every comparison is false on NaN.  The iterates are interior to the cones,
+ * so the returned (y, z) or (x, s) is a certificate that can be checked from
+ * the outputs alone (z in K*, or s in K).  Without the flag nothing changes:
+ * the solver kernels that run are the ones that ran before.
+ * Honoured by socp_batch_solve[_ex], socp_ingest_submit[_csc] and
+ * socp_sqr_solve_socp through params->flags.  Together with
+ * SOCP_F_EXPLICIT_INVERSE the call returns SOCP_E_UNSUPPORTED: in that
+ * operation order the iteration at which the rule fires moves under a one-ulp
+ * change of G.  The register kernel's m > 16 shapes, which
+ * form the inverse by nature, stay supported. */
+#define SOCP_F_DETECT_INFEASIBLE 256
 
 typedef struct socp_ctx socp_ctx;
 
@@ -112,6 +140,10 @@ void* socp_ctx_stream(socp_ctx* ctx);
  * stream stays ordered before later work (an event wait is inserted). */
 int socp_ctx_set_stream(socp_ctx* ctx, void* stream);
 int socp_ctx_reset_stream(socp_ctx* ctx);
+/* tau of SOCP_F_DETECT_INFEASIBLE for every later solve on the context.  The
+ * default is 1e-7 (CVXOPT's feastol).  A non-positive or NaN value returns
+ * SOCP_E_INVALID and leaves the tolerance as it was. */
+int socp_ctx_set_infeasibility_tol(socp_ctx* ctx, double tol);
 
 /* 1 if a compiled kernel accepts the dims: the register-resident kernel (one
  * wavefront per problem, <= 8 cones, m <= 64; k <= 128 for n <= 48, k <= 96
@@ -281,6 +313,9 @@ int socp_sqr_scaling(socp_sqr* h, double* l, double* wbs, double* mu);
  * launching once every problem has stopped (converged or failed); such a call
  * cannot be captured into a HIP graph.  With tol <= 0 (fixed iteration count)
  * it issues only stream-ordered work until the final copies.
+ * params->flags: SOCP_F_DETECT_INFEASIBLE (statuses 5 and 6 stop a problem
+ * like every other status; its res[] is the exit test's, from before the
+ * certificate was scaled).
  * The initial point factors G'G (+ A'A where sing) with W = I: `sing` must be
  * the flag Problem() computes (Socp.jl:49-56, cholesky(G'G) fails).  Where the
  * given flag disagrees and that factorisation fails, the problem stops with
@@ -330,7 +365,9 @@ int socp_pack_csc(socp_ctx* ctx, int64_t batch, int32_t rows, int32_t cols,
  *       arrays in the batch layout above, copied into the slot's pinned
  *       block (no copy for arrays already written at the pointers
  *       socp_ingest_next_inputs returns), then everything is asynchronous.
- *       params->flags other than the defaults are ignored (no warm start).
+ *       Of params->flags, SOCP_F_EXPLICIT_INVERSE and
+ *       SOCP_F_DETECT_INFEASIBLE are honoured (together: SOCP_E_UNSUPPORTED,
+ *       before the slot is claimed); there is no warm start.
  *   socp_ingest_submit_csc(...): A and G as the SparseMatrixCSC arrays of
  *       socp_pack_csc (host pointers; nz_offs[B] - nz_offs[0] nonzeros each),
  *       packed on the device on the copy stream.

@@ -70,6 +70,7 @@ struct socp_ctx {
   int num_cu = 0;
   float last_ms = 0.f;
   const char* last_name = "";
+  double itol = 1e-7;  // SOCP_F_DETECT_INFEASIBLE's tolerance (socp_ctx_set_infeasibility_tol)
   enum { B_C, B_A, B_B, B_G, B_H, B_SING, B_X, B_Y, B_Z, B_S, B_IT, B_ST, B_RES, B_DX, B_DY,
          B_DZ, B_DS, B_CX, B_CY, B_CZ, B_CS, B_CNT, B_LWS, B_ERR, NB };
   DevBuf buf[NB];
@@ -141,6 +142,22 @@ extern "C" int socp_ctx_create(int device, socp_ctx** out) {
 
 extern "C" int socp_ctx_destroy(socp_ctx* c) {
   ctx_free(c);
+  return 0;
+}
+
+extern "C" int socp_ctx_set_infeasibility_tol(socp_ctx* c, double tol) {
+  if (!c) return fail(SOCP_E_INVALID, "ctx is NULL");
+  if (!(tol > 0.0)) return fail(SOCP_E_INVALID, "infeasibility tolerance must be positive");  // NaN too
+  c->itol = tol;
+  return 0;
+}
+
+// SOCP_F_DETECT_INFEASIBLE with SOCP_F_EXPLICIT_INVERSE: refused (include/socp.h)
+static int check_detect_flags(int32_t flags) {
+  if ((flags & SOCP_F_DETECT_INFEASIBLE) && (flags & SOCP_F_EXPLICIT_INVERSE))
+    return fail(SOCP_E_UNSUPPORTED,
+                "SOCP_F_DETECT_INFEASIBLE with SOCP_F_EXPLICIT_INVERSE: the iteration at which the rule fires is "
+                "not stable in the explicit-inverse operation order");
   return 0;
 }
 
@@ -319,7 +336,12 @@ static int launch_small(socp_ctx* ctx, SmallArgs& args, const SmallVariant* v) {
   const bool solver = args.mode == MODE_SOLVE;
   // SOCP_F_EXPLICIT_INVERSE: the sweep variants (m <= 16 shapes; larger m sweep anyway)
   const bool xi = (args.flags & SOCP_F_EXPLICIT_INVERSE) != 0 && v->xi_kernel;
-  const void* kern = xi ? (solver ? v->xi_kernel : v->xi_kkt_kernel) : (solver ? v->kernel : v->kkt_kernel);
+  // SOCP_F_DETECT_INFEASIBLE: the solver instantiation with the rule (never with xi: check_detect_flags)
+  const bool di = solver && !xi && (args.flags & SOCP_F_DETECT_INFEASIBLE) != 0;
+  const void* kern = di   ? v->di_kernel
+                     : xi ? (solver ? v->xi_kernel : v->xi_kkt_kernel)
+                          : (solver ? v->kernel : v->kkt_kernel);
+  if (!kern) return fail(SOCP_E_UNSUPPORTED, "no compiled kernel for these flags");
   if (lds > 64 * 1024)
     HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   int per_cu = 0;
@@ -334,7 +356,7 @@ static int launch_small(socp_ctx* ctx, SmallArgs& args, const SmallVariant* v) {
   HIPCHK(timing_begin(ctx));
   HIPCHK(hipLaunchKernel(kern, dim3((unsigned)blocks), dim3(64), kargs, lds, ctx->stream));
   HIPCHK(timing_end(ctx));
-  ctx->last_name = xi ? (solver ? v->xi_name : v->xi_kkt_name) : (solver ? v->name : v->kkt_name);
+  ctx->last_name = di ? v->di_name : xi ? (solver ? v->xi_name : v->xi_kkt_name) : (solver ? v->name : v->kkt_name);
   return 0;
 }
 
@@ -343,7 +365,8 @@ static int launch_large(socp_ctx* ctx, const SmallArgs& a, double* rec = nullptr
   bool gv = false;
   const bool xi = (a.flags & SOCP_F_EXPLICIT_INVERSE) != 0;
   if (!large_fits(a.n, a.m, a.k, a.nc, &lds, &gv, xi)) return fail(SOCP_E_UNSUPPORTED, kUnsupported);
-  const void* kern = large_kernel_ptr(xi, gv);
+  const bool di = a.mode == MODE_SOLVE && !xi && (a.flags & SOCP_F_DETECT_INFEASIBLE) != 0;
+  const void* kern = large_kernel_ptr(xi, gv, di);
   HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   int per_cu = 0;
   HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 512, lds));
@@ -365,7 +388,7 @@ static int launch_large(socp_ctx* ctx, const SmallArgs& a, double* rec = nullptr
   HIPCHK(timing_begin(ctx));
   HIPCHK(hipLaunchKernel(kern, dim3((unsigned)grid), dim3(512), kargs, lds, ctx->stream));
   HIPCHK(timing_end(ctx));
-  ctx->last_name = large_kernel_name(xi, gv);
+  ctx->last_name = large_kernel_name(xi, gv, di);
   return 0;
 }
 
@@ -492,6 +515,7 @@ extern "C" int socp_batch_solve_ex(socp_ctx* ctx, const socp_dims* dims, const i
     socp_params_default(&P);
   const int64_t B = dims->batch;
   const int n = dims->n, m = dims->m, k = dims->k;
+  TRY(check_detect_flags(P.flags));
   if (B == 0) return 0;
   if (!c || !G || !h || !x || !z || !s || !iters || !status || (m > 0 && (!A || !b || !y)))
     return fail(SOCP_E_INVALID, "NULL data pointer");
@@ -515,6 +539,7 @@ extern "C" int socp_batch_solve_ex(socp_ctx* ctx, const socp_dims* dims, const i
   a.flags = P.flags;
   a.mode = MODE_SOLVE;
   a.deg = degree;
+  if (P.flags & SOCP_F_DETECT_INFEASIBLE) small_set_itol(a, ctx->itol);
   typedef socp_ctx X;
   TRY(stage_in(ctx, X::B_C, c, (size_t)B * n, dev, &a.c));
   TRY(stage_in(ctx, X::B_A, A, (size_t)B * m * n, dev, &a.A));
@@ -1096,6 +1121,7 @@ extern "C" int socp_sqr_solve_socp(socp_sqr* h, const double* c, const double* b
   socp_params P;
   if (params) P = *params; else socp_params_default(&P);
   if (P.maxit < 0) return fail(SOCP_E_INVALID, "maxit < 0");
+  TRY(check_detect_flags(P.flags));
   if (sqr_ipm_lds_bytes(n, m, k) > 160 * 1024)
     return fail(SOCP_E_UNSUPPORTED, "socp_sqr_solve_socp: the IPM kernels' vectors (7 k + n + m doubles) exceed 160 KiB");
   socp_ctx* ctx = h->ctx;
@@ -1145,6 +1171,8 @@ extern "C" int socp_sqr_solve_socp(socp_sqr* h, const double* c, const double* b
   }
   ia.rec = h->a.rec; ia.rec_stride = h->L.rec; ia.r_l = h->L.r_l; ia.r_wb = h->L.r_wb; ia.r_mu = h->L.r_mu;
   ia.tol = P.tol; ia.step = P.step; ia.init_eps = P.init_eps;
+  ia.detect = (P.flags & SOCP_F_DETECT_INFEASIBLE) != 0;
+  ia.itol = ctx->itol;
   // the plugin's own launches on the IPM's buffers
   SqrArgs su = h->a;  // setup_iter(s, z)
   su.s = ia.s; su.z = ia.z; su.status = ia.st_setup; su.active = nullptr;
@@ -1184,6 +1212,8 @@ extern "C" int socp_sqr_solve_socp(socp_sqr* h, const double* c, const double* b
     su.odx = ia.dx; su.ody = ia.dy; su.odz = ia.dz; su.ods = ia.ds; su.ores = ia.res;
     su.ostatus = ia.status; su.oactive = ia.active; su.n_active = ia.n_active;
     su.tol = P.tol;
+    su.detect = ia.detect; su.itol = ia.itol;
+    su.ux = ia.x; su.uy = ia.y; su.uz = ia.z; su.us = ia.s;
   }
   // the wave shapes run the two solves and both step phases in one launch
   const void* solves = SQR_FUSE_SOLVES ? sqr_ipm_solves_kernel_ptr(n, m) : nullptr;
@@ -1744,6 +1774,7 @@ static int ingest_solve(socp_ingest* g, IngestSlot& sl, int64_t B, const uint8_t
   a.flags = P.flags & ~SOCP_F_WARM_START;
   a.mode = MODE_SOLVE;
   a.deg = g->degree;
+  if (P.flags & SOCP_F_DETECT_INFEASIBLE) small_set_itol(a, ctx->itol);
   a.c = (const double*)(din + Li.c);
   a.A = d.m > 0 ? A_dev : nullptr;
   a.b = (const double*)(din + Li.b);
@@ -1782,6 +1813,7 @@ static int ingest_begin(socp_ingest* g, int64_t batch, IngestSlot** out) {
 extern "C" int socp_ingest_submit(socp_ingest* g, int64_t batch, const double* c, const double* A, const double* b,
                                   const double* G, const double* h, const uint8_t* sing, const socp_params* params,
                                   int64_t* ticket) {
+  if (params) TRY(check_detect_flags(params->flags));
   IngestSlot* slp = nullptr;
   TRY(ingest_begin(g, batch, &slp));
   IngestSlot& sl = *slp;
@@ -1820,6 +1852,7 @@ extern "C" int socp_ingest_submit_csc(socp_ingest* g, int64_t batch, const doubl
                                       const int64_t* G_nz_offs, const int64_t* G_colptr, const int64_t* G_rowval,
                                       const double* G_nzval, int32_t index_base, const socp_params* params,
                                       int64_t* ticket) {
+  if (params) TRY(check_detect_flags(params->flags));
   IngestSlot* slp = nullptr;
   TRY(ingest_begin(g, batch, &slp));
   IngestSlot& sl = *slp;

@@ -19,6 +19,9 @@ struct SmallVariant {
   const char* xi_name;
   const void* xi_kkt_kernel;
   const char* xi_kkt_name;
+  // SOCP_F_DETECT_INFEASIBLE (KM 4): the solver with the infeasibility rule
+  const void* di_kernel;
+  const char* di_name;
 };
 
 // table of compiled register-resident variants, ordered by (NQ, NP, MQ)
@@ -107,7 +110,8 @@ struct LargeArgs {
 // xi: the explicit-inverse build (Li = H^-1 by the sweep, SOCP_F_EXPLICIT_INVERSE);
 // gv: the problem's vectors in the HBM workspace instead of LDS (shapes whose
 // vectors exceed a CU's 160 KiB of LDS)
-const void* large_kernel_ptr(bool xi, bool gv);
-const char* large_kernel_name(bool xi, bool gv);
+// di: the solver with the infeasibility rule (SOCP_F_DETECT_INFEASIBLE; not with xi)
+const void* large_kernel_ptr(bool xi, bool gv, bool di = false);
+const char* large_kernel_name(bool xi, bool gv, bool di = false);
 
 }  // namespace socp

@@ -169,7 +169,8 @@ __device__ __forceinline__ d4 tile_mm(const d4& U, const d4& V, d4 C) {
 // (chol_inverse), the reference's operation order (densesolver.jl:47-48),
 // instead of the triangular solves against H = L L'.
 // GV: the vectors in global memory (LV above).
-template <bool XI, bool GV>
+// DI: the solver with the infeasibility rule (SOCP_F_DETECT_INFEASIBLE).
+template <bool XI, bool GV, bool DI = false>
 struct Large {
   static constexpr bool CHOL = SOCP_LG_CHOL && !XI;
   // where Li = H^-1 is formed (XI, and every shape of a SOCP_LG_CHOL=0 build):
@@ -2544,6 +2545,37 @@ struct Large {
     gap = block_sum(zs);
   }
 
+  // SOCP_F_DETECT_INFEASIBLE: the rule of include/socp.h at the iterate whose
+  // residuals were just formed (RD = A'y + G'z + c, RP = Ax - b, DZ = Gx + s - h:
+  // c, b, h are taken out again); five workgroup sums, the same in every thread
+  __device__ int infeas_check(double& scale) {
+    double hz = 0.0, gs2 = 0.0, ax2 = 0.0, aty2 = 0.0, cx = 0.0;
+    for (int i = tid; i < k; i += NTH) {
+      const double hi = LV(H_ + i);
+      const double gs = LV(DZ + i) + hi;
+      hz = fma(hi, LV(Z_ + i), hz);
+      gs2 = fma(gs, gs, gs2);
+    }
+    for (int i = tid; i < m; i += NTH) {
+      const double bi = LV(B_ + i);
+      const double ax = LV(RP + i) + bi;
+      hz = fma(bi, LV(Y_ + i), hz);
+      ax2 = fma(ax, ax, ax2);
+    }
+    for (int j = tid; j < n; j += NTH) {
+      const double cj = LV(C_ + j);
+      const double t = LV(RD + j) - cj;
+      aty2 = fma(t, t, aty2);
+      cx = fma(cj, LV(X_ + j), cx);
+    }
+    hz = block_sum(hz);
+    aty2 = block_sum(aty2);
+    cx = block_sum(cx);
+    ax2 = block_sum(ax2);
+    gs2 = block_sum(gs2);
+    return infeas_verdict(hz, aty2, cx, ax2, gs2, small_itol(a), scale);
+  }
+
   // The matrix part of solve_kkt (densesolver.jl:66-85): n0 = GWiWi*k2 + dx
   // (+A'dy if sing); m0 = A Li n0 - dy; cy = S^-1 m0; m0 = sing ? dy - cy : -cy
   // (init: -cy); cx = Li (n0 + A'm0), taken as Li n0 + (Li A') m0; k1 = G cx - k2.
@@ -2597,6 +2629,7 @@ struct Large {
     LSTAMP(SP_LOAD);
     int status = ST_MAXIT, iters = 0;
     double nd = NAN, np_ = NAN, gap = NAN, ll = 0.0;
+    double isc = 1.0;  // DI: the certificate's factor
     bool dm_aa = false;
     if (a.mode == MODE_SOLVEKKT) {  // solve_kkt against the setup_iter record
       const int st0 = (int)Vr[3 * L.KP + 12 * MAXC + 1];
@@ -2740,6 +2773,13 @@ struct Large {
         status = ST_CONVERGED;
         break;
       }
+      if constexpr (DI) {
+        const int iv = infeas_check(isc);
+        if (iv) {
+          status = iv;
+          break;
+        }
+      }
       for (int j = tid; j < n; j += NTH) LV(RD + j) = -LV(RD + j);
       for (int i = tid; i < m; i += NTH) LV(RP + i) = -LV(RP + i);
       for (int i = tid; i < k; i += NTH) {
@@ -2787,11 +2827,21 @@ struct Large {
       LSTAMP(SP_STEP);
       iters = ++it;
     }
+    if constexpr (DI) {  // the certificate's pair times its factor (1 otherwise: x * 1.0 is x)
+      const double fp = status == ST_DUAL_INF ? isc : 1.0, fd = status == ST_PRIMAL_INF ? isc : 1.0;
+      for (int j = tid; j < n; j += NTH) a.x[p * n + j] = LV(X_ + j) * fp;
+      for (int i = tid; i < m; i += NTH) a.y[p * m + i] = LV(Y_ + i) * fd;
+      for (int i = tid; i < k; i += NTH) {
+        a.z[p * k + i] = LV(Z_ + i) * fd;
+        a.s[p * k + i] = LV(S_ + i) * fp;
+      }
+    } else {
     for (int j = tid; j < n; j += NTH) a.x[p * n + j] = LV(X_ + j);
     for (int i = tid; i < m; i += NTH) a.y[p * m + i] = LV(Y_ + i);
     for (int i = tid; i < k; i += NTH) {
       a.z[p * k + i] = LV(Z_ + i);
       a.s[p * k + i] = LV(S_ + i);
+    }
     }
     if (tid == 0) {
       if (a.res) {
@@ -2810,13 +2860,13 @@ struct Large {
   }
 };
 
-template <bool XI, bool GV>
+template <bool XI, bool GV, bool DI = false>
 __global__ void __launch_bounds__(NTH, 1) socp_large_kernel(LargeArgs args) {
   // the next problem index lives in dynamic LDS (slot 63 of the block-reduction
   // area; GV: slot 0 of the kernel's small LDS): no static LDS, so lg_lds
   // starts at LDS address 0 and the staged SYRK's DMA buffers lie in the
   // first 64 KiB
-  Large<XI, GV> S(args);
+  Large<XI, GV, DI> S(args);
   S.init_tables();
   const int pslot = GV ? 0 : S.L.o_red + 63;
   while (true) {
@@ -2834,17 +2884,23 @@ __global__ void __launch_bounds__(NTH, 1) socp_large_kernel(LargeArgs args) {
 // the global-vector kernels (socp_large_gv.o: this file with SOCP_LG_GV_TU=1)
 template __global__ void socp_large_kernel<false, true>(LargeArgs);
 template __global__ void socp_large_kernel<true, true>(LargeArgs);
+template __global__ void socp_large_kernel<false, true, true>(LargeArgs);
 }  // namespace lg
 #else
 extern template __global__ void socp_large_kernel<false, true>(LargeArgs);
 extern template __global__ void socp_large_kernel<true, true>(LargeArgs);
+extern template __global__ void socp_large_kernel<false, true, true>(LargeArgs);
 }  // namespace lg
 
-const void* large_kernel_ptr(bool xi, bool gv) {
+const void* large_kernel_ptr(bool xi, bool gv, bool di) {
+  if (di && !xi)
+    return gv ? (const void*)&lg::socp_large_kernel<false, true, true>
+              : (const void*)&lg::socp_large_kernel<false, false, true>;
   if (gv) return xi ? (const void*)&lg::socp_large_kernel<true, true> : (const void*)&lg::socp_large_kernel<false, true>;
   return xi ? (const void*)&lg::socp_large_kernel<true, false> : (const void*)&lg::socp_large_kernel<false, false>;
 }
-const char* large_kernel_name(bool xi, bool gv) {
+const char* large_kernel_name(bool xi, bool gv, bool di) {
+  if (di && !xi) return gv ? "socp_large_di_gv_kernel" : "socp_large_di_kernel";
   if (gv) return xi ? "socp_large_xi_gv_kernel" : "socp_large_gv_kernel";
   return xi ? "socp_large_xi_kernel" : "socp_large_kernel";
 }

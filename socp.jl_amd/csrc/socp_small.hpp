@@ -48,8 +48,28 @@ struct ConeTable {
 // (setup_iter :41-52 keeps scaling + H^-1 + S^-1 in a per-problem device
 // record; solve_kkt :54-90 solves one right-hand side against it)
 enum { MODE_SOLVE = 0, MODE_KKT = 1, MODE_SETUP = 2, MODE_SOLVEKKT = 3 };
-enum { ST_CONVERGED = 0, ST_MAXIT = 1, ST_CHOL_H = 2, ST_CHOL_S = 3, ST_DOMAIN = 4 };
-enum { F_WARM = 2 };
+enum { ST_CONVERGED = 0, ST_MAXIT = 1, ST_CHOL_H = 2, ST_CHOL_S = 3, ST_DOMAIN = 4, ST_PRIMAL_INF = 5, ST_DUAL_INF = 6 };
+enum { F_WARM = 2, F_DETECT = 256 };
+
+// SOCP_F_DETECT_INFEASIBLE (include/socp.h): the verdict from the five sums
+// hz = h'z + b'y, |A'y + G'z|^2, cx = c'x, |Ax|^2, |Gx + s|^2 of the iterate.
+// 0, or ST_PRIMAL_INF / ST_DUAL_INF with the factor (1/(-hz), 1/(-cx)) the
+// certificate is returned multiplied by.  Every comparison is false on NaN.
+__host__ __device__ inline int infeas_verdict(double hz, double aty2, double cx, double ax2, double gxs2,
+                                              double tau, double& scale) {
+  if (hz < 0.0 && sqrt(aty2) < tau * -hz) {
+    scale = 1.0 / -hz;
+    return ST_PRIMAL_INF;
+  }
+  if (cx < 0.0) {
+    const double t = tau * -cx;
+    if (sqrt(ax2) < t && sqrt(gxs2) < t) {
+      scale = 1.0 / -cx;
+      return ST_DUAL_INF;
+    }
+  }
+  return 0;
+}
 
 struct SmallArgs {
   int64_t B;
@@ -63,7 +83,7 @@ struct SmallArgs {
   double *x, *y, *z, *s;
   int32_t *iters, *status;
   double* res;
-  const double *dx, *dy, *dz, *ds;
+  const double *dx, *dy, *dz, *ds;  // (MODE_SOLVE with F_DETECT: dx carries the tolerance, small_itol)
   double *cx, *cy, *cz, *cs;
   int32_t* counter;
   double* dbg;                 // optional (KKT mode): per problem H[n*n], Li[n*n], lam[k], wb[k]
@@ -72,6 +92,20 @@ struct SmallArgs {
   double* rec;                 // MODE_SETUP / MODE_SOLVEKKT: per-problem factor records
   int64_t rec_stride;          // doubles per record
 };
+
+// MODE_SOLVE reads no right-hand side: with F_DETECT the slot of dx carries
+// the bits of the infeasibility tolerance, so that the layout of the kernel
+// arguments -- and with it the code of every kernel that does not detect --
+// stays as it was.
+inline void small_set_itol(SmallArgs& a, double tol) {
+  uint64_t u;
+  static_assert(sizeof(u) == sizeof(tol) && sizeof(u) == sizeof(a.dx), "64-bit slot");
+  __builtin_memcpy(&u, &tol, sizeof(u));
+  a.dx = reinterpret_cast<const double*>(static_cast<uintptr_t>(u));
+}
+__device__ __forceinline__ double small_itol(const SmallArgs& a) {
+  return __longlong_as_double(static_cast<long long>(reinterpret_cast<uintptr_t>(a.dx)));
+}
 
 // ------------------------------------------------------------ LDS layout
 // Fixed region (independent of the template shape):
@@ -3302,14 +3336,46 @@ struct Small {
     SYNC();
   }
 
+  // SOCP_F_DETECT_INFEASIBLE: the rule of include/socp.h at the iterate whose
+  // residuals MP_ITER has just formed.  The residual vectors are stored
+  // negated (RD = -(A'y + G'z + c), RP = b - Ax, DZ = h - Gx - s), so
+  // A'y + G'z = -RD - c, Ax = b - RP, Gx + s = h - DZ.  One interleaved
+  // whole-wave scan of the five sums.
+  __device__ __forceinline__ int infeas_check(double& scale) {
+    LANE_IDS();
+    double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = lane; i < k; i += 64) {
+      const double hi = LDS(H_ + i);
+      const double gs = hi - LDS(DZ + i);
+      v[0] = fma(hi, LDS(Z_ + i), v[0]);
+      v[4] = fma(gs, gs, v[4]);
+    }
+    for (int i = lane; i < m; i += 64) {
+      const double bi = LDS(B_ + i);
+      const double ax = bi - LDS(RP + i);
+      v[0] = fma(bi, LDS(Y_ + i), v[0]);
+      v[3] = fma(ax, ax, v[3]);
+    }
+    for (int j = lane; j < n; j += 64) {
+      const double cj = LDS(C_ + j);
+      const double t = -LDS(RD + j) - cj;
+      v[1] = fma(t, t, v[1]);
+      v[2] = fma(cj, LDS(X_ + j), v[2]);
+    }
+    dpp_scan<5>(v, lane, 0, false);
+    return infeas_verdict(readlane_d(v[0], 63), readlane_d(v[1], 63), readlane_d(v[2], 63), readlane_d(v[3], 63),
+                          readlane_d(v[4], 63), small_itol(a), scale);
+  }
+
   // ------------------------------------------------------------- driver
   // solve_socp (solver.jl:40-153) as a micro-phase loop.  solve_kkt
   // (densesolver.jl:54-90) is MP_SOLVE_HEAD -> MP_SOLVE_MAT -> MP_SOLVE_TAIL;
   // `ret` says which solve it is (init, KKT entry, affine, combined).
   // KM = 0: the solver kernel (MODE_SOLVE); KM = 1: the plugin-entry kernel
   // (MODE_KKT, MODE_SETUP, MODE_SOLVEKKT), compiled apart so the solver's
-  // register allocation does not carry the entry paths.
-  template <int KM>
+  // register allocation does not carry the entry paths.  DI: the solver with
+  // SOCP_F_DETECT_INFEASIBLE, an instantiation of its own for the same reason.
+  template <int KM, bool DI = false>
   __device__ __forceinline__ void run(int64_t p) {
     const int mode = KM ? a.mode : (a.mode == MODE_KKT ? (int)MODE_KKT : (int)MODE_SOLVE);
     STAMP(SP_LOAD);
@@ -3319,6 +3385,7 @@ struct Small {
     double ll = 0.0;
     bool fac_ident = false, fac_aa = false, dm_aa = false;
     int fret = 0, ret = 0, fst = 0;
+    double isc = 1.0;  // DI: the certificate's factor
     int after_singtest;
     bool have_sing = false;
     if (mode == MODE_SOLVEKKT) {  // setup_iter failed for this problem: NaN solution, its status
@@ -3471,6 +3538,14 @@ struct Small {
             done = true;
             break;
           }
+          if constexpr (DI) {
+            const int iv = infeas_check(isc);
+            if (iv) {
+              status = iv;
+              done = true;
+              break;
+            }
+          }
           // (rmul!(dx, -1) etc., solver.jl:124: the residuals and ds were stored negated)
           fac_ident = false;
           fac_aa = sing;
@@ -3595,11 +3670,21 @@ struct Small {
       STAMP(SP_STORE);
       return;
     }
+    if constexpr (DI) {  // the certificate's pair times its factor (1 otherwise: x * 1.0 is x)
+      const double fp = status == ST_DUAL_INF ? isc : 1.0, fd = status == ST_PRIMAL_INF ? isc : 1.0;
+      for (int j = lane; j < n; j += 64) a.x[p * n + j] = LDS(X_ + j) * fp;
+      for (int i = lane; i < m; i += 64) a.y[p * m + i] = LDS(Y_ + i) * fd;
+      for (int i = lane; i < k; i += 64) {
+        a.z[p * k + i] = LDS(Z_ + i) * fd;
+        a.s[p * k + i] = LDS(S_ + i) * fp;
+      }
+    } else {
     for (int j = lane; j < n; j += 64) a.x[p * n + j] = LDS(X_ + j);
     for (int i = lane; i < m; i += 64) a.y[p * m + i] = LDS(Y_ + i);
     for (int i = lane; i < k; i += 64) {
       a.z[p * k + i] = LDS(Z_ + i);
       a.s[p * k + i] = LDS(S_ + i);
+    }
     }
     if (lane == 0) {
       if (a.res) {
@@ -3629,12 +3714,13 @@ struct Small {
 };
 
 // KM bit 0: the plugin-entry kernel (MODE_KKT / MODE_SETUP / MODE_SOLVEKKT)
-// instead of the solver; bit 1: the explicit-inverse variant (XI above)
+// instead of the solver; bit 1: the explicit-inverse variant (XI above);
+// bit 2 (KM = 4): the solver with SOCP_F_DETECT_INFEASIBLE
 template <int NQ, int NP, int MQ, int KM>
 #ifndef SOCP_DEV_MINW
 #define SOCP_DEV_MINW 1  // probe builds only: waves per SIMD the register allocation must allow
 #endif
-__global__ void __launch_bounds__(64, KM == 0 ? SOCP_DEV_MINW : 1) socp_small_kernel(SmallArgs args) {
+__global__ void __launch_bounds__(64, (KM & 3) == 0 ? SOCP_DEV_MINW : 1) socp_small_kernel(SmallArgs args) {
   Small<NQ, NP, MQ, (KM & 2) != 0> S(args);
   S.init_tables();
   STAMP_START_S(S);
@@ -3644,7 +3730,7 @@ __global__ void __launch_bounds__(64, KM == 0 ? SOCP_DEV_MINW : 1) socp_small_ke
     p = __shfl(p, 0);
     if ((int64_t)p >= args.B) break;
     S.load_problem(p);
-    S.template run<KM & 1>(p);
+    S.template run<KM & 1, (KM & 4) != 0>(p);
   }
   S.flush_stamps();
 }

@@ -747,8 +747,17 @@ __device__ __forceinline__ void setup_problem(Ctx& C, int64_t p) {
       }
       if (r3[0] + r3[1] + r3[2] < a.tol)
         fin = 0;
-      else if (status != 0)
-        fin = status;
+      else {
+        // SOCP_F_DETECT_INFEASIBLE: after the exit test, before the factorisation's status
+        const int iv = a.detect ? infeas_check_w(n, m, k, a.ic + p * n, a.ib + p * m, a.ih + p * k, a.ux + p * n,
+                                                 a.uy + p * m, a.uz + p * k, a.us + p * k, a.odx + p * n,
+                                                 a.ody + p * m, a.odz + p * k, -1.0, a.itol, lane)
+                                : 0;
+        if (iv)
+          fin = iv;
+        else if (status != 0)
+          fin = status;
+      }
     }
     if (fin >= 0) {
       if (lane == 0) {

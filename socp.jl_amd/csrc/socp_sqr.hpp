@@ -130,6 +130,12 @@ struct SqrArgs {
   double *odx, *ody, *odz, *ods, *ores;  // -rd, -rp, -rz, -lam o lam; ||rd||, ||rp||, z's
   int32_t *ostatus, *oactive, *n_active;
   double tol;
+  // SOCP_F_DETECT_INFEASIBLE (detect != 0, with fuse_resid): the rule follows
+  // the exit test; uz, us, ux, uy are the iterate again, writable, for the
+  // certificate's factor
+  int32_t detect;
+  double itol;
+  double *ux, *uy, *uz, *us;
 };
 
 // the batched solve_socp on the rank-update plugin (socp_sqr_ipm.hip): the
@@ -146,6 +152,8 @@ struct SqrIpmArgs {
   int32_t *status, *iters, *active, *st_setup;
   int32_t* n_active;  // problems still iterating (decremented where active[p] is cleared)
   double tol, step, init_eps;
+  int32_t detect;  // SOCP_F_DETECT_INFEASIBLE: the rule follows the exit test
+  double itol;     // its tolerance
 };
 size_t sqr_ipm_lds_bytes(int n, int m, int k);
 // The wavefront solve kernel reads no H-product chunk buffers: with

@@ -249,6 +249,19 @@ __global__ __launch_bounds__(64) void socp_sqr_ipm_resid_kernel(SqrIpmArgs a) {
     }
     return;
   }
+  if (a.detect) {  // SOCP_F_DETECT_INFEASIBLE: after the exit test, before the factorisation's status
+    const int iv = infeas_check_w(n, m, k, a.c + p * n, a.b + p * m, a.h + p * k, a.x + p * n, a.y + p * m,
+                                  a.z + p * k, a.s + p * k, a.dx + p * n, a.dy + p * m, a.dz + p * k, 1.0, a.itol,
+                                  lane);
+    if (iv) {
+      if (lane == 0) {
+        a.status[p] = iv;
+        a.active[p] = 0;
+        atomicSub(a.n_active, 1);  // the host stops launching once none is left
+      }
+      return;
+    }
+  }
   if (st != 0) {  // cholesky! of H / S failed (PosDefException)
     if (lane == 0) {
       a.status[p] = st;
@@ -290,6 +303,9 @@ __global__ __launch_bounds__(64) void socp_sqr_ipm_final_kernel(SqrIpmArgs a) {
   const int64_t p = blockIdx.x;
   const int lane = threadIdx.x;
   extern __shared__ double lds[];
+  // an infeasibility verdict keeps the exit test's res[]: the quantities at
+  // the iterate before the certificate was multiplied by its factor
+  if (a.status[p] == ST_PRIMAL_INF || a.status[p] == ST_DUAL_INF) return;
   double r3[3];
   residuals_w(a, p, lds, lds + a.n, nullptr, r3, lane);
   if (lane == 0) {

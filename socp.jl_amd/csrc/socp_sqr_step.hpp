@@ -20,6 +20,44 @@ __device__ __forceinline__ void wsy() {
 __device__ __forceinline__ double jmax(double a, double b) { return (isnan(a) || isnan(b)) ? NAN : (a > b ? a : b); }
 __device__ __forceinline__ double jmin(double a, double b) { return (isnan(a) || isnan(b)) ? NAN : (a < b ? a : b); }
 
+// SOCP_F_DETECT_INFEASIBLE (include/socp.h) for one wavefront, from the
+// iterate and the residual vectors the exit test has just formed, read from
+// global memory: rd, rp, rz hold sg (A'y + G'z + c), sg (Ax - b),
+// sg (Gx + s - h) with sg = 1, or -1 where they are stored negated; c, b, h
+// are taken out again.  Returns 0 or the status; on a verdict the
+// certificate's pair (y, z or x, s) is multiplied by its factor in place.
+__device__ int infeas_check_w(int n, int m, int k, const double* c, const double* b, const double* h, double* x,
+                              double* y, double* z, double* s, const double* rd, const double* rp,
+                              const double* rz, double sg, double tau, int lane) {
+  wsy();  // the residual vectors were written by other lanes of this wavefront
+  double hz = 0.0, gs2 = 0.0, ax2 = 0.0, aty2 = 0.0, cx = 0.0;
+  for (int i = lane; i < k; i += 64) {
+    const double gs = sg * rz[i] + h[i];
+    hz = fma(h[i], z[i], hz);
+    gs2 = fma(gs, gs, gs2);
+  }
+  for (int i = lane; i < m; i += 64) {
+    const double ax = sg * rp[i] + b[i];
+    hz = fma(b[i], y[i], hz);
+    ax2 = fma(ax, ax, ax2);
+  }
+  for (int j = lane; j < n; j += 64) {
+    const double t = sg * rd[j] - c[j];
+    aty2 = fma(t, t, aty2);
+    cx = fma(c[j], x[j], cx);
+  }
+  double scale = 1.0;
+  const int iv = infeas_verdict(ws64(hz), ws64(aty2), ws64(cx), ws64(ax2), ws64(gs2), tau, scale);
+  if (iv == ST_PRIMAL_INF) {
+    for (int i = lane; i < m; i += 64) y[i] *= scale;
+    for (int i = lane; i < k; i += 64) z[i] *= scale;
+  } else if (iv == ST_DUAL_INF) {
+    for (int j = lane; j < n; j += 64) x[j] *= scale;
+    for (int i = lane; i < k; i += 64) s[i] *= scale;
+  }
+  return iv;
+}
+
 // vprod! (vectors.jl:58-81): t = u o v, one wavefront
 __device__ void vprod_w(const ConeTable& C, double* t, const double* u, const double* v, int lane) {
   wsy();

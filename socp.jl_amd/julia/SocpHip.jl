@@ -23,6 +23,16 @@ const libsocp = get(ENV, "SOCP_AMD_LIB",
 const SOCP_F_DEVICE_PTRS = Int32(1)
 const SOCP_F_WARM_START = Int32(2)
 const SOCP_F_EXPLICIT_INVERSE = Int32(8)   # Li = H^-1 formed, the reference's op order (densesolver.jl:48)
+# Infeasibility detection (include/socp.h): statuses 5 / 6 with the certificate
+# (y, z scaled to b'y + h'z = -1, or x, s scaled to c'x = -1) in the returned
+# state; not together with SOCP_F_EXPLICIT_INVERSE.  Like the rest of this
+# file, these additions have not been executed here (no Julia in the image).
+const SOCP_F_DETECT_INFEASIBLE = Int32(256)
+const SOCP_PRIMAL_INFEASIBLE = Int32(5)
+const SOCP_DUAL_INFEASIBLE = Int32(6)
+"tau of the detection rule for every later solve of this process's context (default 1e-7)."
+set_infeasibility_tol(tol::Real) =
+    socp_check(ccall((:socp_ctx_set_infeasibility_tol, libsocp), Cint, (Ptr{Cvoid}, Cdouble), socp_ctx(), tol))
 
 struct SocpDims
     batch::Int64
@@ -254,9 +264,13 @@ end
 `solve_socp` (solver.jl:40-153) for every problem of a vector sharing
 `n, m, k` and the cone tuple, in one device call.  Failures are reported per
 problem in `status` (0 converged, 1 maxit, 2/3 PosDef, 4 domain) instead of
-throwing, so one bad problem does not abort the batch.
+throwing, so one bad problem does not abort the batch.  With
+`detect_infeasible=true` a problem without a solution stops with status 5
+(primal infeasible: `y, z` are the certificate) or 6 (dual infeasible: `x, s`
+are the ray) instead of running to `maxit`.
 """
-function solve_socp_batched(problems::AbstractVector{<:Problem}; maxit=40, tol=1e-5, explicit_inverse::Bool=false)
+function solve_socp_batched(problems::AbstractVector{<:Problem}; maxit=40, tol=1e-5, explicit_inverse::Bool=false,
+                            detect_infeasible::Bool=false)
     p0 = problems[1]
     n, m, k = p0.n, p0.m, p0.k
     B = length(problems)
@@ -269,7 +283,9 @@ function solve_socp_batched(problems::AbstractVector{<:Problem}; maxit=40, tol=1
     sing = UInt8[typeof(p).parameters[5] ? 1 : 0 for p in problems]
     x, y, z, s = zeros(B * n), zeros(B * m), zeros(B * k), zeros(B * k)
     iters, status = zeros(Int32, B), zeros(Int32, B)
-    params = Ref(SocpParams(maxit, 3, tol, 0.99, 1e-10, explicit_inverse ? SOCP_F_EXPLICIT_INVERSE : Int32(0), 0))
+    flags = (explicit_inverse ? SOCP_F_EXPLICIT_INVERSE : Int32(0)) |
+            (detect_infeasible ? SOCP_F_DETECT_INFEASIBLE : Int32(0))
+    params = Ref(SocpParams(maxit, 3, tol, 0.99, 1e-10, flags, 0))
     dims = Ref(SocpDims(B, n, m, k, length(p0.cones)))
     rc = ccall((:socp_batch_solve, libsocp), Cint,
                (Ptr{Cvoid}, Ref{SocpDims}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32},
@@ -292,7 +308,8 @@ SolverState(prob, SparseSolver(prob)))` for every problem, the reference's own
 tested configuration, as one device solve (`socp_sqr_create` +
 `socp_sqr_solve_socp`; failures per problem, no throw).
 """
-function solve_socp_batched_sqr(problems::AbstractVector{<:Problem}; maxit=40, tol=1e-5)
+function solve_socp_batched_sqr(problems::AbstractVector{<:Problem}; maxit=40, tol=1e-5,
+                                detect_infeasible::Bool=false)
     p0 = problems[1]
     n, m, k = p0.n, p0.m, p0.k
     B = length(problems)
@@ -311,7 +328,7 @@ function solve_socp_batched_sqr(problems::AbstractVector{<:Problem}; maxit=40, t
                      socp_ctx(), dims, kind, offs, dim, A, G, sing, Int32(0), hd))
     x, y, z, s = zeros(B * n), zeros(B * m), zeros(B * k), zeros(B * k)
     iters, status = zeros(Int32, B), zeros(Int32, B)
-    params = Ref(SocpParams(maxit, 3, tol, 0.99, 1e-10, 0, 0))
+    params = Ref(SocpParams(maxit, 3, tol, 0.99, 1e-10, detect_infeasible ? SOCP_F_DETECT_INFEASIBLE : Int32(0), 0))
     try
         socp_check(ccall((:socp_sqr_solve_socp, libsocp), Cint,
                          (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{SocpParams},

@@ -30,10 +30,19 @@
 #
 # The arithmetic and packing mirror socp.jl_amd/socp_amd/moi.py, which the
 # repository's tests exercise (tests/test_moi.py); this file is not executed
-# here (no Julia in the image).
+# here (no Julia in the image) -- the infeasibility statuses below included.
+#
+# The optimizer solves with infeasibility detection on
+# (SOCP_F_DETECT_INFEASIBLE): status 5 is MOI.INFEASIBLE with the certificate
+# (y, z) as the dual (DualStatus INFEASIBILITY_CERTIFICATE, PrimalStatus
+# NO_SOLUTION), status 6 is MOI.DUAL_INFEASIBLE with the ray (x, s) as the
+# primal (the other way round).
 
 const HIP_STATUS = Dict(0 => MOI.OPTIMAL, 1 => MOI.ITERATION_LIMIT, 2 => MOI.NUMERICAL_ERROR,
-                        3 => MOI.NUMERICAL_ERROR, 4 => MOI.NUMERICAL_ERROR)
+                        3 => MOI.NUMERICAL_ERROR, 4 => MOI.NUMERICAL_ERROR,
+                        5 => MOI.INFEASIBLE, 6 => MOI.DUAL_INFEASIBLE)
+const HIP_PRIMAL_STATUS = Dict(0 => MOI.FEASIBLE_POINT, 5 => MOI.NO_SOLUTION, 6 => MOI.INFEASIBILITY_CERTIFICATE)
+const HIP_DUAL_STATUS = Dict(0 => MOI.FEASIBLE_POINT, 5 => MOI.INFEASIBILITY_CERTIFICATE, 6 => MOI.NO_SOLUTION)
 
 mutable struct HipOptimizer <: MOI.AbstractOptimizer
     inner::Optimizer      # the reference adapter: cone bookkeeping + loaded data
@@ -90,7 +99,7 @@ function optimize_batched!(opts::AbstractVector{HipOptimizer})
     end
     for (key, group) in groups
         probs = [_hip_problem(o.inner) for o in group]
-        states, iters, status = solve_socp_batched(probs; maxit=key[5], tol=key[6])
+        states, iters, status = solve_socp_batched(probs; maxit=key[5], tol=key[6], detect_infeasible=true)
         for (o, st, it, ss) in zip(group, states, iters, status)
             o.inner.sol = st
             o.iters = it
@@ -108,7 +117,9 @@ MOI.get(o::HipOptimizer, ::MOI.TerminationStatus) =
     o.status < 0 ? MOI.OPTIMIZE_NOT_CALLED : HIP_STATUS[o.status]
 MOI.get(o::HipOptimizer, ::MOI.BarrierIterations) = Int(o.iters)
 MOI.get(o::HipOptimizer, ::MOI.PrimalStatus) =
-    MOI.get(o, MOI.TerminationStatus()) == MOI.OPTIMAL ? MOI.FEASIBLE_POINT : MOI.UNKNOWN_RESULT_STATUS
+    o.status < 0 ? MOI.NO_SOLUTION : get(HIP_PRIMAL_STATUS, Int(o.status), MOI.UNKNOWN_RESULT_STATUS)
+MOI.get(o::HipOptimizer, ::MOI.DualStatus) =
+    o.status < 0 ? MOI.NO_SOLUTION : get(HIP_DUAL_STATUS, Int(o.status), MOI.UNKNOWN_RESULT_STATUS)
 MOI.get(o::HipOptimizer, ::MOI.ResultCount) = o.status < 0 ? 0 : 1
 MOI.get(o::HipOptimizer, a::MOI.VariablePrimal, vi::VI) = o.inner.sol.x[vi.value]    # moi.jl:241-243
 MOI.get(o::HipOptimizer, a::MOI.VariablePrimal, vi::Vector{VI}) = MOI.get.(o, Ref(a), vi)

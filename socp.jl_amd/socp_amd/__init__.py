@@ -20,8 +20,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (CHOL_H_FAILED, CHOL_S_FAILED, CONE_POC, CONE_SOC, CONVERGED, DOMAIN_ERROR,
-                   F_DEVICE_PTRS, F_EXPLICIT_INVERSE, F_FORCE_LARGE, F_WARM_START, MAXIT, Context, SocpError,
+from ._lib import (CHOL_H_FAILED, CHOL_S_FAILED, CONE_POC, CONE_SOC, CONVERGED, DOMAIN_ERROR, DUAL_INFEASIBLE,
+                   F_DETECT_INFEASIBLE, F_DEVICE_PTRS, F_EXPLICIT_INVERSE, F_FORCE_LARGE, F_WARM_START, MAXIT,
+                   PRIMAL_INFEASIBLE, Context, SocpError,
                    default_context,
                    default_params)
 
@@ -32,10 +33,12 @@ __all__ = [
     "generate", "pack_csc",
     "Context", "SocpError", "default_context", "cone_arrays",
     "CONVERGED", "MAXIT", "CHOL_H_FAILED", "CHOL_S_FAILED", "DOMAIN_ERROR",
+    "PRIMAL_INFEASIBLE", "DUAL_INFEASIBLE",
 ]
 
 STATUS_NAMES = {CONVERGED: "converged", MAXIT: "maxit", CHOL_H_FAILED: "chol(H) failed",
-                CHOL_S_FAILED: "chol(S) failed", DOMAIN_ERROR: "domain error"}
+                CHOL_S_FAILED: "chol(S) failed", DOMAIN_ERROR: "domain error",
+                PRIMAL_INFEASIBLE: "primal infeasible", DUAL_INFEASIBLE: "dual infeasible"}
 
 
 class PosDefException(Exception):
@@ -119,7 +122,7 @@ def _check_sizes(B, **arrays):
 
 def batch_solve(cones, n, m, k, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5, step=0.99,
                 sigma_exp=3, init_eps=1e-10, warm=None, ctx=None, res=False, out=None, force_large=False,
-                explicit_inverse=False):
+                explicit_inverse=False, detect_infeasible=False):
     """Solve a batch of independent problems (same dims and cone structure).
 
     Arrays follow include/socp.h: per-problem column-major A (m x n), G (k x n)
@@ -130,6 +133,12 @@ def batch_solve(cones, n, m, k, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5,
     register-resident one applies.  explicit_inverse (SOCP_F_EXPLICIT_INVERSE)
     forms Li = H^-1 as densesolver.jl:48 does -- the reference's op order --
     instead of the Cholesky factor + triangular solves of the m <= 16 shapes.
+    detect_infeasible (SOCP_F_DETECT_INFEASIBLE): a problem without a solution
+    stops with status PRIMAL_INFEASIBLE (y, z scaled to b'y + h'z = -1: the
+    certificate) or DUAL_INFEASIBLE (x, s scaled to c'x = -1) once the
+    certificate's residual is below the context's tolerance
+    (Context.set_infeasibility_tol, 1e-7) instead of running to maxit; not
+    together with explicit_inverse.
     Returns dict(x, y, z, s, iters, status[, res]).
     """
     L = _lib.load()
@@ -153,6 +162,8 @@ def batch_solve(cones, n, m, k, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5,
         flags |= F_FORCE_LARGE
     if explicit_inverse:
         flags |= F_EXPLICIT_INVERSE
+    if detect_infeasible:
+        flags |= F_DETECT_INFEASIBLE
     P = default_params(maxit=maxit, tol=tol, step=step, sigma_exp=sigma_exp, init_eps=init_eps,
                        flags=flags)
     if dev:
@@ -361,11 +372,13 @@ class SqrHandle(DenseHandle):
         _lib.check(self._fn("factor")(self.handle, int(problem), _lib.ptr(out)))
         return out.reshape(self.n, self.n, order="F")
 
-    def solve_socp(self, c, b, h, *, maxit=40, tol=1e-5, step=0.99, sigma_exp=3, init_eps=1e-10, res=True):
+    def solve_socp(self, c, b, h, *, maxit=40, tol=1e-5, step=0.99, sigma_exp=3, init_eps=1e-10, res=True,
+                   detect_infeasible=False):
         """solve_socp(prob, SolverState(prob, SparseSolver(prob))) (solver.jl:40-153)
         for every problem of the batch, on this plugin (socp_sqr_solve_socp):
         the reference's own tested path, batched.  Returns dict(x, y, z, s,
-        iters, status[, res]) like ``batch_solve``; numpy or torch as the handle."""
+        iters, status[, res]) like ``batch_solve``; numpy or torch as the handle.
+        detect_infeasible as in ``batch_solve``."""
         B, n, m, k = self.B, self.n, self.m, self.k
         _check_sizes(B, c=(c, B * n), b=(b if m else None, B * m), h=(h, B * k))
         if self.dev:
@@ -384,7 +397,8 @@ class SqrHandle(DenseHandle):
                        iters=np.zeros(B, np.int32), status=np.zeros(B, np.int32))
             if res:
                 out["res"] = np.zeros(3 * B)
-        P = _lib.default_params(maxit=maxit, tol=tol, step=step, sigma_exp=sigma_exp, init_eps=init_eps)
+        P = _lib.default_params(maxit=maxit, tol=tol, step=step, sigma_exp=sigma_exp, init_eps=init_eps,
+                                flags=F_DETECT_INFEASIBLE if detect_infeasible else 0)
         p = _lib.ptr
         _lib.check(self._fn("solve_socp")(self.handle, p(self._arg(c)), p(self._arg(b)) if m else None,
                                            p(self._arg(h)), C.byref(P), p(out["x"]), p(out["y"]) if m else None,
@@ -469,16 +483,18 @@ class Ingest:
             out[key] = np.ctypeslib.as_array(C.cast(q, C.POINTER(ct)), shape=(max(cnt, 1),))[:cnt]
         return out
 
-    def _params(self, maxit, tol, step, sigma_exp, init_eps):
-        return default_params(maxit=maxit, tol=tol, step=step, sigma_exp=sigma_exp, init_eps=init_eps)
+    def _params(self, maxit, tol, step, sigma_exp, init_eps, detect_infeasible=False):
+        return default_params(maxit=maxit, tol=tol, step=step, sigma_exp=sigma_exp, init_eps=init_eps,
+                              flags=F_DETECT_INFEASIBLE if detect_infeasible else 0)
 
-    def submit(self, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5, step=0.99, sigma_exp=3, init_eps=1e-10):
+    def submit(self, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5, step=0.99, sigma_exp=3, init_eps=1e-10,
+               detect_infeasible=False):
         n, m, k = self.n, self.m, self.k
         B = np.size(c) // n
         _check_sizes(B, c=(c, B * n), A=(A if m else None, B * m * n), b=(b if m else None, B * m),
                      G=(G, B * k * n), h=(h, B * k), sing=(sing, B))
         t = C.c_int64()
-        P = self._params(maxit, tol, step, sigma_exp, init_eps)
+        P = self._params(maxit, tol, step, sigma_exp, init_eps, detect_infeasible)
         p = _lib.ptr
         arr = [_host(c), _host(A) if m else None, _host(b) if m else None, _host(G), _host(h),
                None if sing is None else _host(sing, np.uint8)]
@@ -487,7 +503,7 @@ class Ingest:
         return t.value
 
     def submit_csc(self, c, b, h, sing, A_mats, G_mats, *, index_base=1, maxit=40, tol=1e-5, step=0.99,
-                   sigma_exp=3, init_eps=1e-10):
+                   sigma_exp=3, init_eps=1e-10, detect_infeasible=False):
         """A_mats, G_mats: lists of scipy.sparse matrices (m x n, k x n), or
         tuples (nz_offs, colptr, rowval, nzval) of host arrays."""
         n, m, k = self.n, self.m, self.k
@@ -498,7 +514,7 @@ class Ingest:
         Acsc = [np.ascontiguousarray(a) for a in Acsc] if Acsc is not None else [None] * 4
         Gcsc = [np.ascontiguousarray(a) for a in Gcsc]
         t = C.c_int64()
-        P = self._params(maxit, tol, step, sigma_exp, init_eps)
+        P = self._params(maxit, tol, step, sigma_exp, init_eps, detect_infeasible)
         p = _lib.ptr
         _lib.check(_lib.load().socp_ingest_submit_csc(
             self.handle, B, p(_host(c)), p(_host(b) if m else None), p(_host(h)),
@@ -763,11 +779,13 @@ def solve_socp(prob: Problem, ss: SolverState) -> State:
     return State(prob, out["x"], out["y"], out["z"], out["s"])
 
 
-def solve_socp_batched(problems, maxit=40, tol=1e-5, ctx=None, solver="dense"):
+def solve_socp_batched(problems, maxit=40, tol=1e-5, ctx=None, solver="dense", detect_infeasible=False):
     """Batched solve of Problems sharing dims and cones; returns (states, iters, status)
     without raising: failures are reported per problem.  solver="dense": the
     DenseSolver path (the fused register / blocked kernels); "sqr": the
-    SparseSolver rank-update path (SqrHandle.solve_socp)."""
+    SparseSolver rank-update path (SqrHandle.solve_socp).  detect_infeasible as
+    in ``batch_solve``: statuses PRIMAL_INFEASIBLE / DUAL_INFEASIBLE with the
+    certificate in the returned state."""
     p0 = problems[0]
     n, m, k = p0.n, p0.m, p0.k
     for p in problems:
@@ -779,9 +797,11 @@ def solve_socp_batched(problems, maxit=40, tol=1e-5, ctx=None, solver="dense"):
     h = np.concatenate([p.h for p in problems])
     sing = np.array([p.sing for p in problems], np.uint8)
     if solver == "sqr":
-        out = SqrHandle(p0.cones, n, m, k, A, G, sing, ctx=ctx).solve_socp(c, b, h, maxit=maxit, tol=tol)
+        out = SqrHandle(p0.cones, n, m, k, A, G, sing, ctx=ctx).solve_socp(
+            c, b, h, maxit=maxit, tol=tol, detect_infeasible=detect_infeasible)
     else:
-        out = batch_solve(p0.cones, n, m, k, c, A, b, G, h, sing, maxit=maxit, tol=tol, ctx=ctx)
+        out = batch_solve(p0.cones, n, m, k, c, A, b, G, h, sing, maxit=maxit, tol=tol, ctx=ctx,
+                          detect_infeasible=detect_infeasible)
     states = [State(p, out["x"][i * n:(i + 1) * n], out["y"][i * m:(i + 1) * m],
                     out["z"][i * k:(i + 1) * k], out["s"][i * k:(i + 1) * k])
               for i, p in enumerate(problems)]

@@ -17,8 +17,10 @@ HEADER = os.path.join(os.path.dirname(_PKG_ROOT), "include", "socp.h")
 # return codes / statuses / flags (include/socp.h)
 SOCP_OK, SOCP_E_INVALID, SOCP_E_UNSUPPORTED, SOCP_E_HIP, SOCP_E_NOMEM = 0, -1, -2, -3, -4
 CONVERGED, MAXIT, CHOL_H_FAILED, CHOL_S_FAILED, DOMAIN_ERROR = 0, 1, 2, 3, 4
+PRIMAL_INFEASIBLE, DUAL_INFEASIBLE = 5, 6  # with F_DETECT_INFEASIBLE only
 CONE_POC, CONE_SOC = 0, 1
 F_DEVICE_PTRS, F_WARM_START, F_FORCE_LARGE, F_EXPLICIT_INVERSE = 1, 2, 4, 8
+F_DETECT_INFEASIBLE = 256  # bits 16..128 are the CPU oracle's
 
 EXPORTED = [
     "socp_last_error", "socp_version", "socp_params_default", "socp_ctx_create",
@@ -33,7 +35,7 @@ EXPORTED = [
     "socp_ingest_wait", "socp_ingest_destroy",
     "socp_sqr_supported", "socp_sqr_create", "socp_sqr_setup_iter", "socp_sqr_solve_kkt", "socp_sqr_factor",
     "socp_sqr_scaling", "socp_sqr_h2d_bytes", "socp_sqr_record_bytes", "socp_sqr_destroy",
-    "socp_sqr_solve_socp",
+    "socp_sqr_solve_socp", "socp_ctx_set_infeasibility_tol",
 ]
 
 OUTCOME_BYTES = 32  # sizeof(socp_outcome): int32 status, int32 iters, double rd, rp, gap
@@ -95,6 +97,8 @@ def load():
     L.socp_ctx_stream.restype = C.c_void_p
     L.socp_ctx_set_stream.argtypes = [vp, vp]
     L.socp_ctx_reset_stream.argtypes = [vp]
+    if hasattr(L, "socp_ctx_set_infeasibility_tol"):  # infeasibility detection (absent from older A/B builds)
+        L.socp_ctx_set_infeasibility_tol.argtypes = [vp, C.c_double]
     L.socp_supported.argtypes = [C.POINTER(Dims)]
     common = [vp, C.POINTER(Dims), i32p, i32p, i32p]
     L.socp_batch_solve.argtypes = common + [dp] * 5 + [u8p, C.POINTER(Params)] + [dp] * 4 + [i32p, i32p]
@@ -204,6 +208,12 @@ class Context:
         reads them, and torch work issued after it sees the results."""
         import torch
         self.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def set_infeasibility_tol(self, tol: float) -> None:
+        """The tolerance tau of infeasibility detection (detect_infeasible=True)
+        for every later solve on this context; default 1e-7
+        (socp_ctx_set_infeasibility_tol).  Non-positive or NaN raises."""
+        check(load().socp_ctx_set_infeasibility_tol(self.handle, float(tol)))
 
     def last_kernel_ms(self) -> float:
         v = C.c_float()

@@ -30,12 +30,26 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from . import CONVERGED, MAXIT, CHOL_H_FAILED, CHOL_S_FAILED, DOMAIN_ERROR, POC, SOC, batch_solve
+from . import (CONVERGED, MAXIT, CHOL_H_FAILED, CHOL_S_FAILED, DOMAIN_ERROR, PRIMAL_INFEASIBLE, DUAL_INFEASIBLE,
+               POC, SOC, batch_solve)
 
 MIN_SENSE, MAX_SENSE, FEASIBILITY_SENSE = "MIN_SENSE", "MAX_SENSE", "FEASIBILITY_SENSE"
 OPTIMIZE_NOT_CALLED = "OPTIMIZE_NOT_CALLED"
 TERMINATION = {CONVERGED: "OPTIMAL", MAXIT: "ITERATION_LIMIT", CHOL_H_FAILED: "NUMERICAL_ERROR",
-               CHOL_S_FAILED: "NUMERICAL_ERROR", DOMAIN_ERROR: "NUMERICAL_ERROR"}
+               CHOL_S_FAILED: "NUMERICAL_ERROR", DOMAIN_ERROR: "NUMERICAL_ERROR",
+               PRIMAL_INFEASIBLE: "INFEASIBLE", DUAL_INFEASIBLE: "DUAL_INFEASIBLE"}
+# MOI.PrimalStatus / MOI.DualStatus per solver status.  The optimizer solves
+# with infeasibility detection on: a primal-infeasible model returns the
+# certificate (y, z) as its dual (b'y + h'z = -1) and no primal point; a
+# dual-infeasible one the ray (x, s) as its primal (c'x = -1) and no dual.
+FEASIBLE_POINT, NO_SOLUTION, INFEASIBILITY_CERTIFICATE, UNKNOWN_RESULT_STATUS = (
+    "FEASIBLE_POINT", "NO_SOLUTION", "INFEASIBILITY_CERTIFICATE", "UNKNOWN_RESULT_STATUS")
+PRIMAL_STATUS = {CONVERGED: FEASIBLE_POINT, MAXIT: UNKNOWN_RESULT_STATUS, CHOL_H_FAILED: UNKNOWN_RESULT_STATUS,
+                 CHOL_S_FAILED: UNKNOWN_RESULT_STATUS, DOMAIN_ERROR: UNKNOWN_RESULT_STATUS,
+                 PRIMAL_INFEASIBLE: NO_SOLUTION, DUAL_INFEASIBLE: INFEASIBILITY_CERTIFICATE}
+DUAL_STATUS = {CONVERGED: FEASIBLE_POINT, MAXIT: UNKNOWN_RESULT_STATUS, CHOL_H_FAILED: UNKNOWN_RESULT_STATUS,
+               CHOL_S_FAILED: UNKNOWN_RESULT_STATUS, DOMAIN_ERROR: UNKNOWN_RESULT_STATUS,
+               PRIMAL_INFEASIBLE: INFEASIBILITY_CERTIFICATE, DUAL_INFEASIBLE: NO_SOLUTION}
 
 
 # ------------------------------------------------------------------ MOI types
@@ -237,6 +251,12 @@ class Optimizer:
     def termination_status(self) -> str:
         return TERMINATION[self.sol.status] if self.sol is not None else OPTIMIZE_NOT_CALLED
 
+    def primal_status(self) -> str:
+        return PRIMAL_STATUS[self.sol.status] if self.sol is not None else NO_SOLUTION
+
+    def dual_status(self) -> str:
+        return DUAL_STATUS[self.sol.status] if self.sol is not None else NO_SOLUTION
+
     def result_count(self) -> int:
         return 1 if self.sol is not None else 0  # moi.jl:272 (always 1 there)
 
@@ -275,7 +295,8 @@ class Optimizer:
 def optimize_batched(optimizers, ctx=None):
     """`MOI.optimize!` for many models at once: models are grouped by structure
     (n, equality rows, Nonnegatives length, SOC dimensions) and each group is one
-    `socp_batch_solve` launch.  Per-model options `maxit`/`tol` must agree within a group."""
+    `socp_batch_solve` launch, with infeasibility detection on
+    (SOCP_F_DETECT_INFEASIBLE).  Per-model options `maxit`/`tol` must agree within a group."""
     groups: "OrderedDict[tuple, list]" = OrderedDict()
     for o in optimizers:
         d = o.build()
@@ -292,7 +313,7 @@ def optimize_batched(optimizers, ctx=None):
         b = np.concatenate([d.b for d in ds]) if f else None
         G = np.concatenate([d.G.ravel(order="F") for d in ds])
         h = np.concatenate([d.h for d in ds])
-        out = batch_solve(ds[0].cones, n, f, k, c, A, b, G, h, sing, maxit=maxit, tol=tol,
+        out = batch_solve(ds[0].cones, n, f, k, c, A, b, G, h, sing, maxit=maxit, tol=tol, detect_infeasible=True,
                           ctx=ctx if ctx is not None else opts[0].options.get("ctx"))
         for i, o in enumerate(opts):
             o._set_solution(out["x"][i * n:(i + 1) * n], out["y"][i * f:(i + 1) * f],
