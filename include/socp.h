@@ -460,6 +460,18 @@ int socp_debug_set_kkt_dump(double* dev_buf);
  * store, other) and the executed iterations.  The product build ignores it. */
 int socp_debug_set_stamps(unsigned long long* dev_buf);
 
+/* Testing hook (host only, no device work): the slot plan a plain solve of
+ * this cone table takes on the register-resident kernel when k > 64 (the
+ * table is checked as a solve checks it).  The cone vector operations hold a
+ * k-vector as two 64-lane slots; slot s, lane l holds element
+ * (64 s + l - rot) mod k, rot 0 or 64.  kind0 / kind1: 0 mixed, 1 all SOC,
+ * 2 all POC -- both slots are pure, and the solver kernel compiled for that
+ * pair runs, or both are reported mixed and rot is 0.  The environment variable
+ * SOCP_SLOT_SPECIALISE=0 (read at every launch and by this call) forces rot = 0
+ * and the mixed kernel; the results are the same bits. */
+int socp_debug_slot_plan(const socp_dims* dims, const int32_t* kind, const int32_t* offs,
+                         const int32_t* dim, int32_t* rot, int32_t* kind0, int32_t* kind1);
+
 #ifdef __cplusplus
 }
 #endif

@@ -329,6 +329,31 @@ static int cone_rows_uniform(const ConeTable& t, int nc) {
   return d / 16;
 }
 
+// SOCP_SLOT_SPECIALISE=0 (env, read at every launch): the solver kernels take
+// the slots as the cone table lays them out and run the mixed cone code (the
+// A/B of the slot plan; the results are the same bits either way)
+static bool slot_specialise_enabled() {
+  const char* e = getenv("SOCP_SLOT_SPECIALISE");
+  return !(e && e[0] == '0' && e[1] == '\0');
+}
+
+extern "C" int socp_debug_slot_plan(const socp_dims* d, const int32_t* kind, const int32_t* offs,
+                                    const int32_t* dim, int32_t* rot, int32_t* kind0, int32_t* kind1) {
+  ConeTable tab;
+  int deg = 0;
+  if (!rot || !kind0 || !kind1) return fail(SOCP_E_INVALID, "output pointers are NULL");
+  {
+    const int rc = check_problem(d, kind, offs, dim, &tab, &deg);
+    if (rc) return rc;
+  }  // the tables a solve takes, no others
+  int32_t r = 0, kk = 0;
+  small_slot_plan(tab, tab.nc, d->k, cone_rows_uniform(tab, tab.nc), slot_specialise_enabled(), r, kk);
+  *rot = r;
+  *kind0 = kk & 15;
+  *kind1 = kk >> 4;
+  return 0;
+}
+
 static int launch_small(socp_ctx* ctx, SmallArgs& args, const SmallVariant* v) {
   args.al_rows = cone_rows_uniform(args.cones, args.nc);
   size_t lds = small_lds_bytes(v->NQ, v->NP, v->MQ);
@@ -341,6 +366,19 @@ static int launch_small(socp_ctx* ctx, SmallArgs& args, const SmallVariant* v) {
   const void* kern = di   ? v->di_kernel
                      : xi ? (solver ? v->xi_kernel : v->xi_kkt_kernel)
                           : (solver ? v->kernel : v->kkt_kernel);
+  // the slot plan: the plain solver only -- the kernel compiled for the table's pair of pure slots
+  // (the plugin entries keep their records' layout; the xi and di solvers keep their one kernel)
+  args.slot_rot = args.slot_kinds = 0;
+  if (solver && !xi && !di) {
+    int32_t rot = 0, kinds = 0;
+    small_slot_plan(args.cones, args.nc, args.k, args.al_rows, slot_specialise_enabled(), rot, kinds);
+    const int pair = slot_pair_of(kinds & 15, kinds >> 4);
+    if (pair != SLOT_PAIR_NONE && v->slot_kernel[pair - 1]) {
+      kern = v->slot_kernel[pair - 1];
+      args.slot_rot = rot;
+      args.slot_kinds = kinds;
+    }
+  }
   if (!kern) return fail(SOCP_E_UNSUPPORTED, "no compiled kernel for these flags");
   if (lds > 64 * 1024)
     HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

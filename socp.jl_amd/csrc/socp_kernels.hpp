@@ -22,6 +22,9 @@ struct SmallVariant {
   // SOCP_F_DETECT_INFEASIBLE (KM 4): the solver with the infeasibility rule
   const void* di_kernel;
   const char* di_name;
+  // the plain solver compiled for pure slots (KM = SLOT_PAIR_* << 4; two-slot
+  // shapes, NP > 16, else NULL): [SLOT_PAIR_* - 1]
+  const void* slot_kernel[4];
 };
 
 // table of compiled register-resident variants, ordered by (NQ, NP, MQ)

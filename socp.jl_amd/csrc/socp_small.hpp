@@ -91,7 +91,64 @@ struct SmallArgs {
   ConeTable cones;
   double* rec;                 // MODE_SETUP / MODE_SOLVEKKT: per-problem factor records
   int64_t rec_stride;          // doubles per record
+  // solver kernels compiled for pure slots (k > 64, small_slot_plan): the
+  // slots' rotation, 0 or 64, and the pair of kinds the host picked the kernel by
+  int32_t slot_rot, slot_kinds;
 };
+
+// Slot kinds.  The cone vector ops hold a k-vector as two 64-lane slots; slot
+// s, lane l holds element (64 s + l - rot) mod k (only the lanes 64 s + l < k).
+// A slot whose elements are all SOC (all POC) runs only that cone kind's
+// algebra and reductions.  The pair of kinds is a template parameter of the
+// kernel: the mixed kernel carries nothing of the pure ones.
+enum { SLOT_MIXED = 0, SLOT_SOC = 1, SLOT_POC = 2 };
+// pure-slot solver kernels: socp_small_kernel<.., KM = pair << 4>
+enum { SLOT_PAIR_NONE = 0, SLOT_PAIR_SP = 1, SLOT_PAIR_PS = 2, SLOT_PAIR_SS = 3, SLOT_PAIR_PP = 4 };
+constexpr int slot_pair_kind(int pair, int s) {
+  if (pair == SLOT_PAIR_NONE) return SLOT_MIXED;
+  const bool soc = pair == SLOT_PAIR_SS || (pair == SLOT_PAIR_SP && s == 0) || (pair == SLOT_PAIR_PS && s == 1);
+  return soc ? SLOT_SOC : SLOT_POC;
+}
+constexpr int slot_pair_of(int k0, int k1) {
+  return k0 == SLOT_SOC ? (k1 == SLOT_POC ? SLOT_PAIR_SP : (k1 == SLOT_SOC ? SLOT_PAIR_SS : SLOT_PAIR_NONE))
+                        : (k0 == SLOT_POC ? (k1 == SLOT_SOC ? SLOT_PAIR_PS : (k1 == SLOT_POC ? SLOT_PAIR_PP : SLOT_PAIR_NONE))
+                                          : SLOT_PAIR_NONE);
+}
+
+// kind of slot s under rotation rot (k > 64)
+inline int small_slot_kind(const ConeTable& t, int nc, int k, int rot, int s) {
+  bool soc = false, poc = false;
+  for (int p = 64 * s; p < 64 * s + 64 && p < k; ++p) {
+    const int i = (p - rot + k) % k;
+    for (int c = 0; c < nc; ++c)
+      if (i >= t.offs[c] && i < t.offs[c] + t.dim[c]) (t.kind[c] == SOC_K ? soc : poc) = true;
+  }
+  return soc && poc ? (int)SLOT_MIXED : (soc ? (int)SLOT_SOC : (int)SLOT_POC);
+}
+// The launch's slot plan.  Both slots pure as the table stands: rot = 0.
+// Otherwise, when elements 0 .. k-65 are POC and the last 64 are SOC, rot = 64
+// puts the SOC elements in slot 0 and the POC elements in slot 1 -- taken only
+// when every cone is whole 16-lane rows (al_rows != 0), which the rotation by
+// whole rows keeps so, so that every reduction keeps its order.  Otherwise
+// rot = 0 and mixed slots.  Slot bases stay wave-uniform: slot s starts at
+// element (rot ? (s ? 0 : k - 64) : 64 s).
+inline void small_slot_plan(const ConeTable& t, int nc, int k, int al_rows, bool enable, int32_t& rot,
+                            int32_t& kinds) {
+  rot = 0;
+  kinds = 0;
+  if (!enable || k <= 64 || k > KMAX) return;
+  for (int r = 0; r <= 64; r += 64) {
+    if (r && !al_rows) break;
+    const int k0 = small_slot_kind(t, nc, k, r, 0), k1 = small_slot_kind(t, nc, k, r, 1);
+    // (two SOC slots are left to the mixed kernel: that pair's kernel did not repeat the mixed kernel's bits)
+    if (k0 != SLOT_MIXED && k1 != SLOT_MIXED && !(k0 == SLOT_SOC && k1 == SLOT_SOC) &&
+        (r == 0 || (k0 == SLOT_SOC && k1 == SLOT_POC))) {
+      rot = r;
+      kinds = k0 | (k1 << 4);
+      return;
+    }
+  }
+}
 
 // MODE_SOLVE reads no right-hand side: with F_DETECT the slot of dx carries
 // the bits of the infeasibility tolerance, so that the layout of the kernel
@@ -799,9 +856,19 @@ __device__ __forceinline__ void factor_tile(d4 Dt, d4& W, bool& ok, const H& hoo
 // XI (SOCP_F_EXPLICIT_INVERSE): Li = H^-1 formed on every shape -- the
 // reference's operation order (densesolver.jl:47-48 forms Li = L^-T L^-1 from
 // cholesky!(H)) -- instead of the triangular solves of the m <= 16 shapes.
-template <int NQ, int NP, int MQ, bool XI = false>
+// KS0, KS1: the kinds of the two slots this kernel is compiled for (SLOT_*).
+// Mixed (every kernel but the pure-slot solver kernels of the two-slot
+// shapes): the fixed layout, slot s, lane l = element 64 s + l, and cone ops
+// that handle any element.  Pure: SmallArgs::slot_rot is honoured.
+template <int NQ, int NP, int MQ, bool XI = false, int KS0 = SLOT_MIXED, int KS1 = SLOT_MIXED>
 struct Small {
   using SH = Shape<NQ, NP, MQ>;
+  static_assert((KS0 == SLOT_MIXED) == (KS1 == SLOT_MIXED), "both slots pure or both mixed");
+  static_assert(KS0 == SLOT_MIXED || 4 * NP > 64, "pure slots: two-slot shapes only");
+  static constexpr bool SLK = KS0 != SLOT_MIXED;
+  // which algebra a slot of kind KD can need
+  static constexpr bool may_soc(int KD) { return KD != SLOT_POC; }
+  static constexpr bool may_poc(int KD) { return KD != SLOT_SOC; }
   static constexpr int NT = NQ * (NQ + 1) / 2;
   static constexpr int MT = MQ * (MQ + 1) / 2;
   static constexpr int NPAD = SH::NPAD, KP = SH::KP, MPAD = SH::MPAD, LDA = SH::LDA;
@@ -875,6 +942,21 @@ struct Small {
   // O_U + cone(row) * NPAD per k-row (int32, launch-wide: the cone table is
   // the batch's), for the SYRK's U rows (SOCP_SYRK_UBT shapes)
   __device__ __forceinline__ int ubt(int row) const { return reinterpret_cast<const int*>(socp_lds + SH::O_UBT)[row]; }
+  // The element that lane `ln` holds in slot s.  Pure-slot kernels honour the
+  // launch's rotation (SmallArgs::slot_rot, 0 or 64): slot 0 then starts at
+  // element k - 64 and slot 1 at element 0 -- a wave-uniform base per slot,
+  // no wrap inside a slot.  The k-vectors in LDS, G's rows and HBM keep the
+  // problem's order -- only the cone vector ops, which work slot by slot, see
+  // the rotation, so a rotated launch moves no data and no row pass.  The lanes
+  // 64 s + ln >= k hold no element (their index is only read from).
+  __device__ __forceinline__ int el(int s, int ln) const {
+    if constexpr (SLK) {
+      const int base = a.slot_rot ? (s ? 0 : k - 64) : 64 * s;  // wave-uniform
+      return base + ln;
+    } else {
+      return 64 * s + ln;
+    }
+  }
   __device__ __forceinline__ void init_tables() {
     if (lane < nc) {
       LDS(O_COFF + lane) = a.cones.offs[lane];
@@ -909,15 +991,21 @@ struct Small {
     SYNC();
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      const int i = 64 * s + lane;
-      const bool ev = i < k;
+      const int i = el(s, lane);
+      const bool ev = 64 * s + lane < k;
       const int code = ev ? (int)LDS(O_RC + i) : 3;
       const int c = ev ? (code >> 2) : 0;
       ci[s] = c;
       kd[s] = ev ? (code & 3) : 3;
-      const int o = ev ? (int)LDS(O_COFF + c) : i;
+      const int eo_ = ev ? (int)LDS(O_COFF + c) : i;
       const int d = ev ? (int)LDS(O_CDIM + c) : 1;
-      eo[s] = o;
+      eo[s] = eo_;  // the cone's first element (its index in the k-vectors)
+      // the cone's lanes: from its first position in the slots, eo_ rotated
+      int o = eo_;
+      if constexpr (SLK) {
+        const int rot = a.slot_rot;  // 0 or 64
+        o = eo_ + rot >= k && rot ? eo_ + rot - k : eo_ + rot;
+      }
       const int st = o > 64 * s ? o : 64 * s;
       const int en = (o + d) < 64 * (s + 1) ? (o + d) : 64 * (s + 1);
       spn[s] = ev && o < 64 && o + d > 64;
@@ -1071,24 +1159,52 @@ struct Small {
   // hide each other's latency); the DPP moves write every lane, so no old value
   // is materialised (lanes a pattern leaves unwritten fail the step's
   // predicate); all partials are read before any is used.
-  template <int NV, unsigned MX>
+  // Live masks (L0, L1: bit q set = value q of slot 0 / 1 is needed): a pure
+  // slot hands the reductions only the values its cone kind uses.  The values
+  // are reduced independently of each other, so leaving some out changes no
+  // result; with every bit set the code is the unmasked one.
+  static constexpr unsigned LIVE_ALL = ~0u;
+  static constexpr bool live(unsigned L0, unsigned L1, int s, int q) { return (((s ? L1 : L0) >> q) & 1u) != 0; }
+  static constexpr int live_pos(unsigned L0, unsigned L1, int NV, int s, int q) {
+    int c = 0;
+    for (int t = 0; t < 2; ++t)
+      for (int r = 0; r < NV; ++r) {
+        if (t == s && r == q) return c;
+        if (live(L0, L1, t, r)) ++c;
+      }
+    return c;
+  }
+  static constexpr int live_count(unsigned L0, unsigned L1, int NS, int NV) { return live_pos(L0, L1, NV, NS, 0); }
+  static constexpr unsigned live_mx(unsigned MX, unsigned L0, unsigned L1, int NS, int NV) {
+    unsigned m = 0;
+    for (int t = 0; t < NS; ++t)
+      for (int r = 0; r < NV; ++r)
+        if (live(L0, L1, t, r) && ((MX >> r) & 1u)) m |= 1u << live_pos(L0, L1, NV, t, r);
+    return m;
+  }
+  template <int NV, unsigned MX, unsigned L0 = LIVE_ALL, unsigned L1 = LIVE_ALL>
   __device__ __forceinline__ void cone_reduce(double (&v)[2][NV]) {
     MARK_BEGIN("cone_reduce");
     LANE_IDS();
     constexpr int NS = KP > 64 ? 2 : 1;  // slots that can hold elements of this shape
     if (a.al_rows) {  // row-aligned cones: registers only
       const int R = a.al_rows;
-      constexpr unsigned MXM = NS == 2 ? (MX | (MX << NV)) : MX;
-      double w[NS * NV];
+      constexpr int NL = live_count(L0, L1, NS, NV);
+      constexpr unsigned MXM = live_mx(MX, L0, L1, NS, NV);
+      if constexpr (NL > 0) {
+        double w[NL];
 #pragma unroll
-      for (int s = 0; s < NS; ++s)
+        for (int s = 0; s < NS; ++s)
 #pragma unroll
-        for (int q = 0; q < NV; ++q) w[s * NV + q] = v[s][q];
-      cone_allreduce_rows_n<NS * NV, MXM>(w, R);
+          for (int q = 0; q < NV; ++q)
+            if (live(L0, L1, s, q)) w[live_pos(L0, L1, NV, s, q)] = v[s][q];
+        cone_allreduce_rows_n<NL, MXM>(w, R);
 #pragma unroll
-      for (int s = 0; s < NS; ++s)
+        for (int s = 0; s < NS; ++s)
 #pragma unroll
-        for (int q = 0; q < NV; ++q) v[s][q] = w[s * NV + q];
+          for (int q = 0; q < NV; ++q)
+            if (live(L0, L1, s, q)) v[s][q] = w[live_pos(L0, L1, NV, s, q)];
+      }
       return;
     }
     const int rl = lane & 15;
@@ -1097,6 +1213,7 @@ struct Small {
     const int st = ssl[s];                                               \
     const bool ok_ = (OK);                                               \
     _Pragma("unroll") for (int q = 0; q < NV; ++q) {                     \
+      if (!live(L0, L1, s, q)) continue;                                 \
       const double y = dpp_all<CTRL>(v[s][q]);                           \
       const double r = ((MX >> q) & 1) ? fmax(v[s][q], y) : v[s][q] + y; \
       v[s][q] = ok_ ? r : v[s][q];                                       \
@@ -1113,7 +1230,8 @@ struct Small {
     for (int s = 0; s < NS; ++s) {
       if (lane == sle[s]) {
 #pragma unroll
-        for (int q = 0; q < NV; ++q) LDS(O_PART + (q * NCS + ci[s]) * 2 + s) = v[s][q];
+        for (int q = 0; q < NV; ++q)
+          if (live(L0, L1, s, q)) LDS(O_PART + (q * NCS + ci[s]) * 2 + s) = v[s][q];
       }
     }
     SYNC();
@@ -1122,6 +1240,7 @@ struct Small {
     for (int s = 0; s < NS; ++s)
 #pragma unroll
       for (int q = 0; q < NV; ++q) {
+        if (!live(L0, L1, s, q)) continue;
         pp[s][q][0] = LDS(O_PART + (q * NCS + ci[s]) * 2);
         pp[s][q][1] = LDS(O_PART + (q * NCS + ci[s]) * 2 + 1);
       }
@@ -1129,6 +1248,7 @@ struct Small {
     for (int s = 0; s < NS; ++s)
 #pragma unroll
       for (int q = 0; q < NV; ++q) {
+        if (!live(L0, L1, s, q)) continue;
         const double p0 = pp[s][q][0], p1 = pp[s][q][1];
         const double both = ((MX >> q) & 1) ? fmax(p0, p1) : p0 + p1;
         v[s][q] = spn[s] ? both : (s == 0 ? p0 : p1);
@@ -1139,7 +1259,7 @@ struct Small {
   // two slot partials of every cone in O_PART; cone_tot(q, c) adds them (the
   // unused (cone, slot) entries stay zero).  For per-cone work done once per
   // cone (on "cone lanes", lane c < nc) instead of once per element.
-  template <int NV>
+  template <int NV, unsigned L0 = LIVE_ALL, unsigned L1 = LIVE_ALL>
   __device__ __forceinline__ void cone_partials(double (&v)[2][NV]) {
     MARK_BEGIN("cone_partials");
     LANE_IDS();
@@ -1147,22 +1267,28 @@ struct Small {
     const int rl = lane & 15;
     if (a.al_rows) {  // row-aligned cones: every lane of the cone gets its total
       const int R = a.al_rows;
-      double w[NS * NV];
+      constexpr int NL = live_count(L0, L1, NS, NV);
+      if constexpr (NL > 0) {
+        double w[NL];
 #pragma unroll
-      for (int s = 0; s < NS; ++s)
+        for (int s = 0; s < NS; ++s)
 #pragma unroll
-        for (int q = 0; q < NV; ++q) w[s * NV + q] = v[s][q];
-      cone_allreduce_rows_n<NS * NV, 0u>(w, R);
+          for (int q = 0; q < NV; ++q)
+            if (live(L0, L1, s, q)) w[live_pos(L0, L1, NV, s, q)] = v[s][q];
+        cone_allreduce_rows_n<NL, 0u>(w, R);
 #pragma unroll
-      for (int s = 0; s < NS; ++s)
+        for (int s = 0; s < NS; ++s)
 #pragma unroll
-        for (int q = 0; q < NV; ++q) v[s][q] = w[s * NV + q];
+          for (int q = 0; q < NV; ++q)
+            if (live(L0, L1, s, q)) v[s][q] = w[live_pos(L0, L1, NV, s, q)];
+      }
     } else {
 #define SOCP_SCAN_STEP(CTRL, OK)                         \
   _Pragma("unroll") for (int s = 0; s < NS; ++s) {       \
     const int st = ssl[s];                               \
     const bool ok_ = (OK);                               \
     _Pragma("unroll") for (int q = 0; q < NV; ++q) {     \
+      if (!live(L0, L1, s, q)) continue;                 \
       const double y = dpp_all<CTRL>(v[s][q]);           \
       v[s][q] = ok_ ? v[s][q] + y : v[s][q];             \
     }                                                    \
@@ -1179,7 +1305,8 @@ struct Small {
     for (int s = 0; s < NS; ++s) {
       if (lane == sle[s]) {
 #pragma unroll
-        for (int q = 0; q < NV; ++q) LDS(O_PART + (q * NCS + ci[s]) * 2 + s) = v[s][q];
+        for (int q = 0; q < NV; ++q)
+          if (live(L0, L1, s, q)) LDS(O_PART + (q * NCS + ci[s]) * 2 + s) = v[s][q];
       }
     }
     SYNC();
@@ -1205,6 +1332,30 @@ struct Small {
   // 1e-9, and these replace IEEE divisions in per-element and per-cone math)
   __device__ __forceinline__ static double rcp_nr(double d) { return recip(d); }
 
+  // ---- slot kinds.  Each cone vector op below is a template over the kinds
+  // (SL0, SL1) of the two slots, instantiated with the kernel's (KS0, KS1): no
+  // branch, one copy of each op per kernel.  In the body, for slot s:
+  //   pocs(K, kd): "take the POC value" -- constant in a pure slot (true in a
+  //                POC slot, where the lanes without an element compute values
+  //                nobody stores), the type code's test in a mixed one;
+  //   pocm(K, kd): a POC element is here (a mask: stores, reduction inputs);
+  //   tailm / headm: an SOC tail / head element is here, never in a POC slot.
+  // The compiler drops the other kind's chain, its constant reads and the
+  // selects between the two.  (SL0, SL1) = mixed is the code as it was.
+#define SOCP_SK(s) ((s) == 0 ? SL0 : SL1)
+  // Rounding: the per-slot bodies below run with FMA contraction off and name
+  // every fused product themselves.  Left to -ffp-contract=fast, each compiled
+  // instance of a body (slot 0's and slot 1's, mixed and pure) fuses a*b + c*d
+  // its own way, and an element then rounds differently depending on the slot
+  // it sits in -- a rotated launch would not repeat the bits of a plain one.
+  // The code outside these bodies holds no other sum of two products (the cone
+  // lanes' nsum is named too); single products fuse the same way everywhere.
+  static __device__ __forceinline__ bool pocs(int K, int kd_) { return may_poc(K) && (!may_soc(K) || kd_ == 0); }
+  static __device__ __forceinline__ bool pocm(int K, int kd_) { return may_poc(K) && kd_ == 0; }
+  static __device__ __forceinline__ bool tailm(int K, int kd_) { return may_soc(K) && kd_ == 2; }
+  static __device__ __forceinline__ bool headm(int K, int kd_) { return may_soc(K) && kd_ == 1; }
+#define SOCP_SLOT_DISPATCH(F, ...) return F<KS0, KS1>(__VA_ARGS__)
+
   // compute_scaling (scalings.jl:22-110) and ds = lam o lam (solver.jl:120).
   // Writes WB (wbar / sqrt(s/z)), LAM, IL (1/lambda of the POC elements), the
   // X = W^-1 G row coefficients CA, CBV, DS (write_ds: the iteration's
@@ -1216,6 +1367,10 @@ struct Small {
   // the coefficients of the tail rows) runs once per cone on lane c, not once
   // per element.
   __device__ __forceinline__ bool scaling_op(double& ll, bool& dm_aa, bool write_ds) {
+    SOCP_SLOT_DISPATCH(scaling_op_k, ll, dm_aa, write_ds);
+  }
+  template <int SL0, int SL1>
+  __device__ __forceinline__ bool scaling_op_k(double& ll, bool& dm_aa, bool write_ds) {
     MARK_BEGIN("scaling_op");
     if (SOCP_KO & 4096) {
       ll = 1.0;
@@ -1226,15 +1381,15 @@ struct Small {
     double v[2][3], zi[2], si[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      const int i = 64 * s + lane;
+      const int i = el(s, lane);
       zi[s] = LDS(Z_ + i);
       si[s] = LDS(S_ + i);
-      const bool tail = kd[s] == 2;
+      const bool tail = tailm(SOCP_SK(s), kd[s]);
       v[s][0] = tail ? zi[s] * zi[s] : 0.0;
       v[s][1] = tail ? si[s] * si[s] : 0.0;
       v[s][2] = tail ? zi[s] * si[s] : 0.0;
     }
-    cone_partials<3>(v);
+    cone_partials<3, may_soc(SL0) ? 7u : 0u, may_soc(SL1) ? 7u : 0u>(v);
     MARK_BEGIN("scal_cone1");
     bool dm = false;
     // ---- cone lanes: the SOC branch of compute_scaling (scalings.jl:32-99)
@@ -1246,7 +1401,7 @@ struct Small {
       const double fz = rsqrt_nr(onrmz), fs = rsqrt_nr(onrms);
       const double nrmz = onrmz * fz, nrms = onrms * fs;
       const double zb0 = z0 * fz, sb0 = s0 * fs;
-      const double nsum = zb0 * sb0 + cone_tot(2, c) * fz * fs;
+      const double nsum = fma(zb0, sb0, cone_tot(2, c) * fz * fs);  // (named: two products, one sum)
       const double garg = (1.0 + nsum) * 0.5;
       const double rg = rsqrt_nr(garg);
       const double gamma = garg * rg;
@@ -1277,33 +1432,34 @@ struct Small {
     double li[2], wbi[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      const int i = 64 * s + lane, c = ci[s];
-      const bool poc = kd[s] == 0, tail = kd[s] == 2;
+#pragma clang fp contract(off)
+      const int i = el(s, lane), c = ci[s];
+      const bool poc = pocs(SOCP_SK(s), kd[s]), pm = pocm(SOCP_SK(s), kd[s]), tail = tailm(SOCP_SK(s), kd[s]);
       // POC: one 1/sqrt(s z) gives sqrt(s/z) = s q, sqrt(z/s) = z q, sqrt(s z) = (s z) q
       const double pr = si[s] * zi[s];
       const double q = rsqrt_nr(pr);
       const double as = ccv(CC_AS, c), az = ccv(CC_AZ, c), bs = ccv(CC_BS, c), bz = ccv(CC_BZ, c);
       const double imu = ccv(CC_IMU, c), l0 = ccv(CC_L0, c);
-      const double wt = si[s] * as - zi[s] * az;
-      const double lt = si[s] * bs + zi[s] * bz;
-      dm = dm || (poc && pr < 0.0);
+      const double wt = fma(si[s], as, -(zi[s] * az));
+      const double lt = fma(si[s], bs, zi[s] * bz);
+      dm = dm || (pm && pr < 0.0);
       wbi[s] = poc ? zmul(si[s], q) : (tail ? wt : ccv(CC_WB0, c));
       li[s] = poc ? zmul(pr, q) : (tail ? lt : l0);
-      if (poc || tail) {
+      if (pm || tail) {
         LDS(WB + i) = wbi[s];
         LDS(LAM + i) = li[s];
         LDS(CA + i) = poc ? zmul(zi[s], q) : imu;
         LDS(CBV + i) = poc ? 0.0 : wt * imu;
-        if (poc) LDS(IL + i) = q;
-        if (write_ds) LDS(DS + i) = -(poc ? li[s] * li[s] : (l0 * li[s] + l0 * li[s]));  // -ds: the RHS
+        if (pm) LDS(IL + i) = q;
+        if (write_ds) LDS(DS + i) = -(poc ? li[s] * li[s] : fma(l0, li[s], l0 * li[s]));  // -ds: the RHS
       }
       // lam o lam head (vprod!, vectors.jl:58-75) and |lambda_1|^2 (POC: the
       // cone's sum of lambda_i^2, its share of lam'lam), |wbar_1|^2, wbar_1'lambda_1
-      v[s][0] = (poc || tail) ? li[s] * li[s] : 0.0;
+      v[s][0] = (pm || tail) ? li[s] * li[s] : 0.0;
       v[s][1] = tail ? wbi[s] * wbi[s] : 0.0;
       v[s][2] = tail ? wbi[s] * li[s] : 0.0;
     }
-    cone_partials<3>(v);
+    cone_partials<3, may_soc(SL0) ? 7u : 1u, may_soc(SL1) ? 7u : 1u>(v);
     MARK_BEGIN("scal_cone2");
     bool da = false;
     double tl = 0.0;
@@ -1353,7 +1509,7 @@ struct Small {
     const double fz = rsqrt_nr(onrmz), fs = rsqrt_nr(onrms);
     const double nrmz = onrmz * fz, nrms = onrms * fs;
     const double zb0 = z0 * fz, sb0 = s0 * fs;
-    const double nsum = zb0 * sb0 + cone_tot(2, c) * fz * fs;
+    const double nsum = fma(zb0, sb0, cone_tot(2, c) * fz * fs);  // (named: two products, one sum)
     const double garg = (1.0 + nsum) * 0.5;
     const double rg = rsqrt_nr(garg);
     const double gamma = garg * rg;
@@ -1409,6 +1565,10 @@ struct Small {
   // latency).  The same operations as residuals() then scaling_op(): the
   // results are bitwise the same.  Returns the DomainError flag.
   __device__ __forceinline__ bool resid_scaling(double& nd, double& np_, double& gap, double& ll, bool& dm_aa) {
+    SOCP_SLOT_DISPATCH(resid_scaling_k, nd, np_, gap, ll, dm_aa);
+  }
+  template <int SL0, int SL1>
+  __device__ __forceinline__ bool resid_scaling_k(double& nd, double& np_, double& gap, double& ll, bool& dm_aa) {
     MARK_BEGIN("resid_scaling");
     LANE_IDS();
     constexpr int NS = KP > 64 ? 2 : 1;
@@ -1419,7 +1579,7 @@ struct Small {
       xq[q] = LDS(X_ + 16 * q + cl);
     }
 #pragma unroll
-    for (int t = 0; t < NS; ++t) {
+    for (int t = 0; t < NS; ++t) {  // z's: summed over the fixed pairing 64 t + lane, rotated slots or not
       zv[t] = LDS(Z_ + 64 * t + lane);
       sv[t] = LDS(S_ + 64 * t + lane);
     }
@@ -1427,15 +1587,15 @@ struct Small {
     double v[2][3], zi[2], si[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      const int i = 64 * s + lane;
+      const int i = el(s, lane);
       zi[s] = LDS(Z_ + i);
       si[s] = LDS(S_ + i);
-      const bool tail = kd[s] == 2;
+      const bool tail = tailm(SOCP_SK(s), kd[s]);
       v[s][0] = tail ? zi[s] * zi[s] : 0.0;
       v[s][1] = tail ? si[s] * si[s] : 0.0;
       v[s][2] = tail ? zi[s] * si[s] : 0.0;
     }
-    cone_partials<3>(v);
+    cone_partials<3, may_soc(SL0) ? 7u : 0u, may_soc(SL1) ? 7u : 0u>(v);
     // ---- the cone-lane chain inside G'z's first batch
     const bool socl = HOIST_CST ? lc_soc : (lane < nc && (int)LDS(O_CKIND + lane) == SOC_K);
     const int cc_ = lane < nc ? lane : 0;
@@ -1451,31 +1611,32 @@ struct Small {
     double li[2], wbi[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      const int i = 64 * s + lane, c = ci[s];
-      const bool poc = kd[s] == 0, tail = kd[s] == 2;
+#pragma clang fp contract(off)
+      const int i = el(s, lane), c = ci[s];
+      const bool poc = pocs(SOCP_SK(s), kd[s]), pm = pocm(SOCP_SK(s), kd[s]), tail = tailm(SOCP_SK(s), kd[s]);
       const double pr = si[s] * zi[s];
       const double q = rsqrt_nr(pr);
       const double as = ccv(CC_AS, c), az = ccv(CC_AZ, c), bs = ccv(CC_BS, c), bz = ccv(CC_BZ, c);
       const double imu = ccv(CC_IMU, c), l0 = ccv(CC_L0, c);
-      const double wt = si[s] * as - zi[s] * az;
-      const double lt = si[s] * bs + zi[s] * bz;
-      dm = dm || (poc && pr < 0.0);
+      const double wt = fma(si[s], as, -(zi[s] * az));
+      const double lt = fma(si[s], bs, zi[s] * bz);
+      dm = dm || (pm && pr < 0.0);
       wbi[s] = poc ? zmul(si[s], q) : (tail ? wt : ccv(CC_WB0, c));
       li[s] = poc ? zmul(pr, q) : (tail ? lt : l0);
-      if (poc || tail) {
+      if (pm || tail) {
         LDS(WB + i) = wbi[s];
         LDS(LAM + i) = li[s];
         LDS(CA + i) = poc ? zmul(zi[s], q) : imu;
         LDS(CBV + i) = poc ? 0.0 : wt * imu;
-        if (poc) LDS(IL + i) = q;
-        LDS(DS + i) = -(poc ? li[s] * li[s] : (l0 * li[s] + l0 * li[s]));  // -ds: the RHS
+        if (pm) LDS(IL + i) = q;
+        LDS(DS + i) = -(poc ? li[s] * li[s] : fma(l0, li[s], l0 * li[s]));  // -ds: the RHS
       }
-      v[s][0] = (poc || tail) ? li[s] * li[s] : 0.0;
+      v[s][0] = (pm || tail) ? li[s] * li[s] : 0.0;
       v[s][1] = tail ? wbi[s] * wbi[s] : 0.0;
       v[s][2] = tail ? wbi[s] * li[s] : 0.0;
     }
     At_mv(Y_, at);
-    cone_partials<3>(v);
+    cone_partials<3, may_soc(SL0) ? 7u : 1u, may_soc(SL1) ? 7u : 1u>(v);
     // ---- rd, the second cone-lane part beside A x and G x + s - h
     double d2 = 0.0, zs = 0.0;
     if (g == 0) {
@@ -1543,21 +1704,23 @@ struct Small {
   // wbar_1'k1_1 = mu (delta + (k0_0 + delta/(1+wbar_0)) |wbar_1|^2), and the
   // second W^-1 reuses the first one's dot.  POC: k0 = ds / lambda by the
   // reciprocal kept in IL.  In: DS, DZ.  Out: K0, K2, T2, DLT (per cone).
-  __device__ __forceinline__ void solve_head() {
+  __device__ __forceinline__ void solve_head() { SOCP_SLOT_DISPATCH(solve_head_k); }
+  template <int SL0, int SL1>
+  __device__ __forceinline__ void solve_head_k() {
     MARK_BEGIN("solve_head");
     if (SOCP_KO & 8192) return;
     LANE_IDS();
     double v[2][3], x[2], x0[2], dz[2], dz0[2], lam[2], wb[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      const int i = 64 * s + lane;
+      const int i = el(s, lane);
       x[s] = LDS(DS + i);
       x0[s] = LDS(DS + eo[s]);
       dz[s] = LDS(DZ + i);
       dz0[s] = LDS(DZ + eo[s]);
       lam[s] = LDS(LAM + i);
       wb[s] = LDS(WB + i);
-      const bool tail = kd[s] == 2;
+      const bool tail = tailm(SOCP_SK(s), kd[s]);
       v[s][0] = tail ? lam[s] * x[s] : 0.0;
       v[s][1] = tail ? wb[s] * x[s] : 0.0;
       v[s][2] = tail ? wb[s] * dz[s] : 0.0;
@@ -1568,7 +1731,7 @@ struct Small {
     auto read_cst = [&]() {
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      const int i = 64 * s + lane, c = ci[s];
+      const int i = el(s, lane), c = ci[s];
       cst[s][0] = ccv(CC_L0, c);
       cst[s][1] = ccv(CC_IAA, c);
       cst[s][2] = ccv(CC_IL0, c);
@@ -1584,12 +1747,13 @@ struct Small {
     }
     };
     if constexpr (HOIST_CST) read_cst();
-    cone_reduce<3, 0>(v);
+    cone_reduce<3, 0, may_soc(SL0) ? 7u : 0u, may_soc(SL1) ? 7u : 0u>(v);
     STAMP_X(8);
     MARK_BEGIN("head_post");
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      const int i = 64 * s + lane, c = ci[s];
+#pragma clang fp contract(off)
+      const int i = el(s, lane), c = ci[s];
       const double t = v[s][0], u = v[s][1], w = v[s][2];
 #define CST(j, expr) (HOIST_CST ? cst[s][j] : (expr))
       const double l0 = CST(0, ccv(CC_L0, c)), iaa = CST(1, ccv(CC_IAA, c)), il0 = CST(2, ccv(CC_IL0, c)),
@@ -1598,27 +1762,28 @@ struct Small {
                    i1 = CST(7, ccv(CC_I1, c));
       const double w2 = CST(8, ccv(CC_W2, c)), wl = CST(9, ccv(CC_WL, c));
       // iprod! (vectors.jl:105-125)
-      const double k00 = (x0[s] * l0 - t) * iaa;
-      const double k0t = -(x0[s] * lam[s] * iaa) + x[s] * il0 + lam[s] * t * il0aa;
-      const double dlt = -(x0[s] * wl * iaa) + u * il0 + wl * t * il0aa;  // wbar_1'k0_1
+      const double k00 = fma(x0[s], l0, -t) * iaa;
+      const double k0t = fma(lam[s] * t, il0aa, fma(x[s], il0, -(x0[s] * lam[s] * iaa)));
+      const double dlt = fma(wl * t, il0aa, fma(u, il0, -(x0[s] * wl * iaa)));  // wbar_1'k0_1
       // scale! (scalings.jl:159-165)
-      const double k10 = mu * (wb0 * k00 + dlt);
-      const double k1t = mu * (k0t + (k00 + dlt * i1) * wb[s]);
+      const double kd1 = fma(dlt, i1, k00);  // k0_0 + delta/(1+wbar_0)
+      const double k10 = mu * fma(wb0, k00, dlt);
+      const double k1t = mu * fma(kd1, wb[s], k0t);
       const double k20 = dz0[s] - k10;
-      const double a1 = w - mu * (dlt + (k00 + dlt * i1) * w2);  // wbar_1'k2_1
+      const double a1 = fma(-mu, fma(kd1, w2, dlt), w);  // wbar_1'k2_1 = w - mu (delta + kd1 |wbar_1|^2)
       // iscale! twice (scalings.jl:167-173)
-      const double cy = a1 * i1 - k20;
-      const double y0 = imu * (wb0 * k20 - a1);
-      const double a2 = imu * (a1 + cy * w2);
+      const double cy = fma(a1, i1, -k20);
+      const double y0 = imu * fma(wb0, k20, -a1);
+      const double a2 = imu * fma(cy, w2, a1);
       // POC: elementwise, with 1/lambda and 1/w = CA
       const double k0p = x[s] * CST(10, LDS(IL + i));
-      const double k2p = dz[s] - wb[s] * k0p;
+      const double k2p = fma(-wb[s], k0p, dz[s]);
       const double ca = CST(11, LDS(CA + i));
-      const bool poc = kd[s] == 0, hd = kd[s] == 1;
+      const bool poc = pocs(SOCP_SK(s), kd[s]), hd = headm(SOCP_SK(s), kd[s]);
       const double k0 = poc ? k0p : (hd ? k00 : k0t);
       const double k2 = poc ? k2p : dz[s] - (hd ? k10 : k1t);
-      const double yt = imu * (k2 + cy * wb[s]);
-      const double zs = hd ? imu * (wb0 * y0 - a2) : imu * (yt + (a2 * i1 - y0) * wb[s]);
+      const double yt = imu * fma(cy, wb[s], k2);
+      const double zs = hd ? imu * fma(wb0, y0, -a2) : imu * fma(fma(a2, i1, -y0), wb[s], yt);
       if (kd[s] != 3) {
         LDS(K0 + i) = k0;
         LDS(K2 + i) = k2;
@@ -1640,6 +1805,10 @@ struct Small {
   // T1 = kt3, K0 = kt2, KK (per cone), O_TOTC[1][0] = kt2'kt3, the step
   // length (dom: DomainError).
   __device__ __forceinline__ double solve_tail(bool do_step, bool dm_aa, int& dom) {
+    SOCP_SLOT_DISPATCH(solve_tail_k, do_step, dm_aa, dom);
+  }
+  template <int SL0, int SL1>
+  __device__ __forceinline__ double solve_tail_k(bool do_step, bool dm_aa, int& dom) {
     MARK_BEGIN("solve_tail");
     if (SOCP_KO & 16384) {
       dom = 0;
@@ -1649,14 +1818,14 @@ struct Small {
     double v[2][3], k1[2], k10[2], k0[2], k00[2], wb[2], lam[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      const int i = 64 * s + lane;
+      const int i = el(s, lane);
       k1[s] = LDS(K1 + i);
       k10[s] = LDS(K1 + eo[s]);
       k0[s] = LDS(K0 + i);
       k00[s] = LDS(K0 + eo[s]);
       wb[s] = LDS(WB + i);
       lam[s] = LDS(LAM + i);
-      const bool tail = kd[s] == 2;
+      const bool tail = tailm(SOCP_SK(s), kd[s]);
       v[s][0] = tail ? wb[s] * k1[s] : 0.0;
       v[s][1] = tail ? lam[s] * k1[s] : 0.0;
       v[s][2] = tail ? lam[s] * k0[s] : 0.0;
@@ -1665,7 +1834,7 @@ struct Small {
     auto read_cst = [&]() {
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      const int i = 64 * s + lane, c = ci[s];
+      const int i = el(s, lane), c = ci[s];
       cst[s][0] = ccv(CC_MU, c);
       cst[s][1] = ccv(CC_IMU, c);
       cst[s][2] = ccv(CC_WB0, c);
@@ -1681,31 +1850,32 @@ struct Small {
     }
     };
     if constexpr (HOIST_CST) read_cst();
-    cone_reduce<3, 0>(v);
+    cone_reduce<3, 0, may_soc(SL0) ? 7u : 0u, may_soc(SL1) ? 7u : 0u>(v);
     STAMP_X(9);
     MARK_BEGIN("tail_post1");
     double y[2], y0v[2], kn[2], kn0[2], ly[2], lkn[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      const int i = 64 * s + lane, c = ci[s];
+#pragma clang fp contract(off)
+      const int i = el(s, lane), c = ci[s];
       const double a1 = v[s][0];
       const double mu = CST(0, ccv(CC_MU, c)), imu = CST(1, ccv(CC_IMU, c)), wb0 = CST(2, ccv(CC_WB0, c)),
                    i1 = CST(3, ccv(CC_I1, c));
       const double w2 = CST(4, ccv(CC_W2, c)), wl = CST(5, ccv(CC_WL, c));
       const double ca = CST(6, LDS(CA + i));
-      const bool poc = kd[s] == 0, hd = kd[s] == 1;
-      const double cy = a1 * i1 - k10[s];
-      const double y0 = imu * (wb0 * k10[s] - a1);
-      const double a2 = imu * (a1 + cy * w2);  // wbar_1'y_1
-      y[s] = poc ? ca * k1[s] : (hd ? y0 : imu * (k1[s] + cy * wb[s]));
-      const double zs = hd ? imu * (wb0 * y0 - a2) : imu * (y[s] + (a2 * i1 - y0) * wb[s]);
+      const bool poc = pocs(SOCP_SK(s), kd[s]), hd = headm(SOCP_SK(s), kd[s]);
+      const double cy = fma(a1, i1, -k10[s]);
+      const double y0 = imu * fma(wb0, k10[s], -a1);
+      const double a2 = imu * fma(cy, w2, a1);  // wbar_1'y_1
+      y[s] = poc ? ca * k1[s] : (hd ? y0 : imu * fma(cy, wb[s], k1[s]));
+      const double zs = hd ? imu * fma(wb0, y0, -a2) : imu * fma(fma(a2, i1, -y0), wb[s], y[s]);
       y0v[s] = y0;
       kn[s] = k0[s] - y[s];
       kn0[s] = k00[s] - y0;
       const double del = CST(7, ccv(CC_DLT, c)) - a2;  // wbar_1'kn_1
       const double cs = poc ? wb[s] * kn[s]
-                            : (hd ? mu * (wb0 * kn0[s] + del) : mu * (kn[s] + (kn0[s] + del * i1) * wb[s]));
-      ly[s] = imu * (v[s][1] + cy * wl);  // lambda_1'y_1
+                            : (hd ? mu * fma(wb0, kn0[s], del) : mu * fma(fma(del, i1, kn0[s]), wb[s], kn[s]));
+      ly[s] = imu * fma(cy, wl, v[s][1]);  // lambda_1'y_1
       lkn[s] = v[s][2] - ly[s];           // lambda_1'kn_1
       if (kd[s] != 3) {
         LDS(RZ + i) = poc ? ca * y[s] : zs;
@@ -1720,17 +1890,18 @@ struct Small {
     double w[2][5], r1y[2], r1k[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      const int i = 64 * s + lane, c = ci[s];
+#pragma clang fp contract(off)
+      const int i = el(s, lane), c = ci[s];
       if (kd[s] != 3) {
         LDS(T1 + i) = y[s];
         LDS(K0 + i) = kn[s];
       }
-      const bool tail = kd[s] == 2, poc = kd[s] == 0, real = kd[s] != 3;
+      const bool tail = tailm(SOCP_SK(s), kd[s]), poc = pocm(SOCP_SK(s), kd[s]), real = kd[s] != 3;
       const double sa = CST(8, ccv(CC_SA, c)), l0 = CST(9, ccv(CC_L0, c)), sal = CST(10, ccv(CC_SAL, c));
-      r1y[s] = sa * l0 * y0v[s] - sa * ly[s];
-      r1k[s] = sa * l0 * kn0[s] - sa * lkn[s];
+      r1y[s] = fma(sa * l0, y0v[s], -(sa * ly[s]));
+      r1k[s] = fma(sa * l0, kn0[s], -(sa * lkn[s]));
       const double cyy = (r1y[s] + y0v[s]) * sal, cyk = (r1k[s] + kn0[s]) * sal;
-      const double qy = sa * (y[s] - cyy * sa * lam[s]), qk = sa * (kn[s] - cyk * sa * lam[s]);
+      const double qy = sa * fma(-(cyy * sa), lam[s], y[s]), qk = sa * fma(-(cyk * sa), lam[s], kn[s]);
       const double il = CST(11, LDS(IL + i));
       w[s][0] = tail ? qy * qy : 0.0;
       w[s][1] = tail ? qk * qk : 0.0;
@@ -1738,18 +1909,21 @@ struct Small {
       w[s][3] = poc ? -kn[s] * il : -INFINITY;
       w[s][4] = real ? y[s] * kn[s] : 0.0;
     }
-    cone_reduce<5, 0xC>(w);
+    // SOC: |q_y|^2, |q_k|^2; POC: the two maxima; both: the cone's kt2'kt3
+    cone_reduce<5, 0xC, may_soc(SL0) ? (may_poc(SL0) ? 0x1Fu : 0x13u) : 0x1Cu,
+                may_soc(SL1) ? (may_poc(SL1) ? 0x1Fu : 0x13u) : 0x1Cu>(w);
     STAMP_X(10);
     MARK_BEGIN("tail_post2");
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
+#pragma clang fp contract(off)
       const int c = ci[s];
-      if (64 * s >= k || kd[s] == 3 || 64 * s + lane != eo[s]) continue;
+      if (64 * s >= k || kd[s] == 3 || el(s, lane) != eo[s]) continue;
       const double sa = CST(8, ccv(CC_SA, c));
 #undef CST
-      const double vy = sqrt_nr(w[s][0]) - sa * r1y[s];
-      const double vk = sqrt_nr(w[s][1]) - sa * r1k[s];
-      LDS(O_TOTC + c) = kd[s] == 0 ? fmax(w[s][2], w[s][3]) : fmax(vy, vk);
+      const double vy = fma(-sa, r1y[s], sqrt_nr(w[s][0]));
+      const double vk = fma(-sa, r1k[s], sqrt_nr(w[s][1]));
+      LDS(O_TOTC + c) = pocs(SOCP_SK(s), kd[s]) ? fmax(w[s][2], w[s][3]) : fmax(vy, vk);
       LDS(cc(CC_KK, c)) = w[s][4];
     }
     SYNC();
@@ -1762,7 +1936,9 @@ struct Small {
   // (:136-140): kt1 = kt2 o kt3, ds += sigma mu e - kt1, dx, dy, dz *= 1 - sigma.
   // kt2'kt3 and the SOC heads of kt2 o kt3 come from solve_tail's reduction.
   // In: K0 (kt2), T1 (kt3), KK, DS, DZ, RD, RP.
-  __device__ __forceinline__ void affine_post(double tstep, double ll) {
+  __device__ __forceinline__ void affine_post(double tstep, double ll) { SOCP_SLOT_DISPATCH(affine_post_k, tstep, ll); }
+  template <int SL0, int SL1>
+  __device__ __forceinline__ void affine_post_k(double tstep, double ll) {
     MARK_BEGIN("affine_post");
     if (SOCP_KO & 32768) return;
     LANE_IDS();
@@ -1783,7 +1959,7 @@ struct Small {
       double a2[2], a3[2], a20[2], a30[2], kkc[2], dsv[2], dzv[2];
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        const int i = 64 * s + lane;
+        const int i = el(s, lane);
         a2[s] = LDS(K0 + i);
         a3[s] = LDS(T1 + i);
         a20[s] = LDS(K0 + eo[s]);
@@ -1795,11 +1971,13 @@ struct Small {
       const double rdv = LDS(RD + lane), rpv = LDS(RP + (lane < MPAD ? lane : 0));
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        const int i = 64 * s + lane;
+#pragma clang fp contract(off)
+        const int i = el(s, lane);
         if (kd[s] == 3) continue;
-        const double kt1 = kd[s] == 0 ? a2[s] * a3[s] : (kd[s] == 1 ? kkc[s] : a20[s] * a3[s] + a30[s] * a2[s]);
-        const double e = kd[s] == 2 ? 0.0 : 1.0;
-        LDS(DS + i) = dsv[s] + (smu * e - kt1);
+        const double kt1 = pocs(SOCP_SK(s), kd[s]) ? a2[s] * a3[s]
+                                                   : (headm(SOCP_SK(s), kd[s]) ? kkc[s] : fma(a20[s], a3[s], a30[s] * a2[s]));
+        const double e = tailm(SOCP_SK(s), kd[s]) ? 0.0 : 1.0;
+        LDS(DS + i) = dsv[s] + (smu * e - kt1);  // (smu e is exact)
         LDS(DZ + i) = dzv[s] * scf;
       }
       if (lane < n) LDS(RD + lane) = rdv * scf;
@@ -1808,11 +1986,12 @@ struct Small {
     } else {
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        const int i = 64 * s + lane;
+#pragma clang fp contract(off)
+        const int i = el(s, lane);
         if (kd[s] == 3) continue;
         const double a2 = LDS(K0 + i), a3 = LDS(T1 + i);
         const double a20 = LDS(K0 + eo[s]), a30 = LDS(T1 + eo[s]);
-        const double kt1 = kd[s] == 0 ? a2 * a3 : (kd[s] == 1 ? LDS(cc(CC_KK, ci[s])) : a20 * a3 + a30 * a2);
+        const double kt1 = kd[s] == 0 ? a2 * a3 : (kd[s] == 1 ? LDS(cc(CC_KK, ci[s])) : fma(a20, a3, a30 * a2));
         const double e = kd[s] == 2 ? 0.0 : 1.0;
         LDS(DS + i) = LDS(DS + i) + (smu * e - kt1);
         LDS(DZ + i) = LDS(DZ + i) * scf;
@@ -1825,24 +2004,28 @@ struct Small {
 
   // max_step(-iz), max_step(iz) (mats.jl:1-28) for the initial shift (solver.jl:88-101)
   __device__ __forceinline__ void maxstep_op(int xv, double& alphp, double& alphd) {
+    SOCP_SLOT_DISPATCH(maxstep_op_k, xv, alphp, alphd);
+  }
+  template <int SL0, int SL1>
+  __device__ __forceinline__ void maxstep_op_k(int xv, double& alphp, double& alphd) {
     MARK_BEGIN("maxstep_op");
     LANE_IDS();
     double v[2][3], x[2], x0[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      const int i = 64 * s + lane;
+      const int i = el(s, lane);
       x[s] = LDS(xv + i);
       x0[s] = LDS(xv + eo[s]);
-      v[s][0] = kd[s] == 2 ? x[s] * x[s] : 0.0;
-      v[s][1] = kd[s] == 0 ? x[s] : -INFINITY;
-      v[s][2] = kd[s] == 0 ? -x[s] : -INFINITY;
+      v[s][0] = tailm(SOCP_SK(s), kd[s]) ? x[s] * x[s] : 0.0;
+      v[s][1] = pocm(SOCP_SK(s), kd[s]) ? x[s] : -INFINITY;
+      v[s][2] = pocm(SOCP_SK(s), kd[s]) ? -x[s] : -INFINITY;
     }
-    cone_reduce<3, 0x6>(v);
+    cone_reduce<3, 0x6, may_soc(SL0) ? (may_poc(SL0) ? 7u : 1u) : 6u, may_soc(SL1) ? (may_poc(SL1) ? 7u : 1u) : 6u>(v);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      if (64 * s >= k || kd[s] == 3 || 64 * s + lane != eo[s]) continue;
+      if (64 * s >= k || kd[s] == 3 || el(s, lane) != eo[s]) continue;
       const double nr = sqrt_nr(v[s][0]);
-      const bool poc = kd[s] == 0;
+      const bool poc = pocs(SOCP_SK(s), kd[s]);
       LDS(O_TOTC + ci[s]) = poc ? v[s][1] : nr + x0[s];
       LDS(O_TOTC + NCS + ci[s]) = poc ? v[s][2] : nr - x0[s];
     }
@@ -3713,6 +3896,7 @@ struct Small {
   }
 };
 
+// KM bits 4..: the pure-slot solver kernels (KM = SLOT_PAIR_* << 4, plain solver only);
 // KM bit 0: the plugin-entry kernel (MODE_KKT / MODE_SETUP / MODE_SOLVEKKT)
 // instead of the solver; bit 1: the explicit-inverse variant (XI above);
 // bit 2 (KM = 4): the solver with SOCP_F_DETECT_INFEASIBLE
@@ -3721,7 +3905,7 @@ template <int NQ, int NP, int MQ, int KM>
 #define SOCP_DEV_MINW 1  // probe builds only: waves per SIMD the register allocation must allow
 #endif
 __global__ void __launch_bounds__(64, (KM & 3) == 0 ? SOCP_DEV_MINW : 1) socp_small_kernel(SmallArgs args) {
-  Small<NQ, NP, MQ, (KM & 2) != 0> S(args);
+  Small<NQ, NP, MQ, (KM & 2) != 0, slot_pair_kind(KM >> 4, 0), slot_pair_kind(KM >> 4, 1)> S(args);
   S.init_tables();
   STAMP_START_S(S);
   while (true) {

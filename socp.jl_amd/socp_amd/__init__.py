@@ -92,6 +92,20 @@ def cone_arrays(cones):
     return kind, offs, dim
 
 
+def slot_plan(cones, k):
+    """(rot, kind0, kind1) of socp_debug_slot_plan: how the register-resident
+    solver lays a k > 64 cone table over its two 64-lane slots (kinds: 0 mixed,
+    1 all SOC, 2 all POC).  Host only."""
+    kind, offs, dim = cone_arrays(cones)
+    d = _lib.Dims(1, 1, 0, int(k), len(kind))
+    rot, k0, k1 = C.c_int32(), C.c_int32(), C.c_int32()
+    rc = _lib.load().socp_debug_slot_plan(C.byref(d), kind.ctypes.data, offs.ctypes.data, dim.ctypes.data,
+                                          C.byref(rot), C.byref(k0), C.byref(k1))
+    if rc:
+        raise SocpError(rc, _lib.load().socp_last_error().decode())
+    return rot.value, k0.value, k1.value
+
+
 # --------------------------------------------------------------- batched
 def _is_torch(a):
     return a is not None and not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")

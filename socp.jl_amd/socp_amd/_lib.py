@@ -35,7 +35,7 @@ EXPORTED = [
     "socp_ingest_wait", "socp_ingest_destroy",
     "socp_sqr_supported", "socp_sqr_create", "socp_sqr_setup_iter", "socp_sqr_solve_kkt", "socp_sqr_factor",
     "socp_sqr_scaling", "socp_sqr_h2d_bytes", "socp_sqr_record_bytes", "socp_sqr_destroy",
-    "socp_sqr_solve_socp", "socp_ctx_set_infeasibility_tol",
+    "socp_sqr_solve_socp", "socp_ctx_set_infeasibility_tol", "socp_debug_slot_plan",
 ]
 
 OUTCOME_BYTES = 32  # sizeof(socp_outcome): int32 status, int32 iters, double rd, rp, gap
@@ -100,6 +100,8 @@ def load():
     if hasattr(L, "socp_ctx_set_infeasibility_tol"):  # infeasibility detection (absent from older A/B builds)
         L.socp_ctx_set_infeasibility_tol.argtypes = [vp, C.c_double]
     L.socp_supported.argtypes = [C.POINTER(Dims)]
+    if hasattr(L, "socp_debug_slot_plan"):  # (absent from older A/B builds)
+        L.socp_debug_slot_plan.argtypes = [C.POINTER(Dims), i32p, i32p, i32p] + [C.POINTER(C.c_int32)] * 3
     common = [vp, C.POINTER(Dims), i32p, i32p, i32p]
     L.socp_batch_solve.argtypes = common + [dp] * 5 + [u8p, C.POINTER(Params)] + [dp] * 4 + [i32p, i32p]
     L.socp_batch_solve_ex.argtypes = common + [dp] * 5 + [u8p, C.POINTER(Params)] + [dp] * 4 + [i32p, i32p, dp]
