@@ -354,8 +354,23 @@ extern "C" int socp_debug_slot_plan(const socp_dims* d, const int32_t* kind, con
   return 0;
 }
 
+// SOCP_FUSE_U=0 (env, read at every launch): the SYRK's cone rows U are formed
+// by compute_U() in factor() on every table, as before the residuals' G x pass
+// learnt to form them (the A/B of the fusion; the results are the same bits)
+static bool fuse_u_enabled() {
+  const char* e = getenv("SOCP_FUSE_U");
+  return !(e && e[0] == '0' && e[1] == '\0');
+}
+
 static int launch_small(socp_ctx* ctx, SmallArgs& args, const SmallVariant* v) {
   args.al_rows = cone_rows_uniform(args.cones, args.nc);
+  // (cones of 32 or 64 rows on a variant of whole 8-row-step chunks: a G x chunk lies in one cone)
+  args.fuse_u = 0;
+  if (args.al_rows >= 2 && v->NP % 8 == 0 && fuse_u_enabled()) {
+    args.fuse_u = 0x100;
+    for (int c = 0; c < args.nc && c < NCS; ++c)
+      if (args.cones.kind[c] == SOC_K) args.fuse_u |= 1 << c;
+  }
   size_t lds = small_lds_bytes(v->NQ, v->NP, v->MQ);
   if (lds > 160 * 1024) return fail(SOCP_E_UNSUPPORTED, "LDS footprint too large");
   const bool solver = args.mode == MODE_SOLVE;

@@ -94,6 +94,10 @@ struct SmallArgs {
   // solver kernels compiled for pure slots (k > 64, small_slot_plan): the
   // slots' rotation, 0 or 64, and the pair of kinds the host picked the kernel by
   int32_t slot_rot, slot_kinds;
+  // nonzero: the residuals' G x pass forms the SYRK's cone rows U (gemv_G_chunk<.., FU>):
+  // bit 8, and bit c for every SOC cone c.  The host sets it only with al_rows >= 2,
+  // cones of 32 or 64 rows (env SOCP_FUSE_U=0 clears it)
+  int32_t fuse_u;
 };
 
 // Slot kinds.  The cone vector ops hold a k-vector as two 64-lane slots; slot
@@ -229,7 +233,14 @@ struct Shape {
   static constexpr int O_NV = O_A + MPAD * LDA;    // n-vectors: c x rd rx n0 tn
   static constexpr int O_MV = O_NV + 6 * NPAD;     // m-vectors: b y rp ry m0 tm
   // U[NCS][NPAD] (the SYRK's cone rows) and, for m <= 16, A Li (MPAD x LDA,
-  // from the Schur step to the solves): their lifetimes do not overlap
+  // from the Schur step to the solves): their lifetimes do not overlap.
+  // Z' / A Li is written by factor() after form_H and last read by the
+  // combined solve; U is written either by compute_U() in factor() or, on
+  // fused launches (SmallArgs::fuse_u), by the G x pass of the next
+  // iteration's residuals -- after that last read -- and read by form_H only.
+  // Nothing between the residuals and form_H touches the region (the exit
+  // tests and infeas_check read k-, n- and m-vectors only), on the Cholesky,
+  // the explicit-inverse and the detecting solvers alike.
   static constexpr bool AL_LDS = MQ == 1;
   static constexpr int UAL = (AL_LDS && MPAD * LDA > NCS * NPAD) ? MPAD * LDA : NCS * NPAD;
   static constexpr int O_U = O_MV + 6 * MPAD;
@@ -635,6 +646,15 @@ struct RSCount<C, 0> {
   static constexpr int value = C;
 };
 
+// what factor() factors: the scaling's H with U still to form (compute_U), the
+// identity scaling's (U = 0), or the scaling's with U already in LDS -- formed by
+// the residuals' G x pass of the same MP_ITER visit (launches with
+// SmallArgs::fuse_u).  The kind is chosen by the phase that asks for the
+// factorisation, for that factorisation alone: a problem that leaves MP_ITER
+// after U was formed (exit test, DomainError, infeasibility rule, the residuals
+// after the last iteration) asks for none, and nothing is carried to the
+// wave's next problem.
+enum : int { FAC_SCALED, FAC_IDENT, FAC_SCALED_U };
 // driver micro-phases and solve kinds
 enum : int {
   MP_SINGTEST, MP_SINGTEST_POST, MP_FACTOR, MP_INIT, MP_ITER, MP_KKT,
@@ -716,6 +736,9 @@ __device__ __forceinline__ double rsqrt_tile(double d) {
 #endif
 #ifndef SOCP_U_LANECONES
 #define SOCP_U_LANECONES 1  // compute_U takes the cone descriptors from the cone lanes (0: from the kernel args)
+#endif
+#ifndef SOCP_FUSE_U
+#define SOCP_FUSE_U 1  // the residuals' G x pass can form U (SmallArgs::fuse_u); 0: compute_U() always (A/B builds)
 #endif
 #ifndef SOCP_TILE_OKDIAG
 #define SOCP_TILE_OKDIAG 1  // the pivot test once per tile, on the diagonal of W (0: per pivot)
@@ -938,6 +961,13 @@ struct Small {
       : a(args), lane(threadIdx.x), g(threadIdx.x >> 4), cl(threadIdx.x & 15),
         n(args.n), m(args.m), k(args.k), nc(args.nc) {}
 
+#ifndef SOCP_KO
+#define SOCP_KO 0  // timing knock-outs (tuning builds only; results are wrong): 1 G loaded once per wave,
+                   // 2 no residuals, 4 no U (neither compute_U nor the residuals' fused form), 8 no S factorisation, 16 no Gx, 32 no G'z (residuals),
+                   // 128 no A products (residuals), 256 no triangular solves, 512 / 1024 no G products
+                   // in the solves, 2048 no S solves, 4096 no scaling, 8192 no solve head,
+                   // 16384 no solve tail, 32768 no corrector, 65536 no SYRK (H = I), 131072 no chol
+#endif
   // ---------------------------------------------------------------- setup
   // O_U + cone(row) * NPAD per k-row (int32, launch-wide: the cone table is
   // the batch's), for the SYRK's U rows (SOCP_SYRK_UBT shapes)
@@ -1014,13 +1044,6 @@ struct Small {
     }
   }
 
-#ifndef SOCP_KO
-#define SOCP_KO 0  // timing knock-outs (tuning builds only; results are wrong): 1 G loaded once per wave,
-                   // 2 no residuals, 4 no compute_U, 8 no S factorisation, 16 no Gx, 32 no G'z (residuals),
-                   // 128 no A products (residuals), 256 no triangular solves, 512 / 1024 no G products
-                   // in the solves, 2048 no S solves, 4096 no scaling, 8192 no solve head,
-                   // 16384 no solve tail, 32768 no corrector, 65536 no SYRK (H = I), 131072 no chol
-#endif
   bool ko_gloaded = false;
   // lane c < nc: its cone's kind and offset (per-cone work without the table
   // round trips)
@@ -1661,7 +1684,16 @@ struct Small {
       const double sa = rsqrt_nr(aa);
       const double w2 = cone_tot(1, cc_), wl = cone_tot(2, cc_);
       const double iaa = recip(aa), il0 = recip(l0), il0aa = recip(l0 * aa), sal = recip(sa * l0 + 1.0);
-      gemv_G_r<true>(xq, S_, H_, DZ);
+      // Fused launches: the pass forms U as well -- WB and CC_I1 of this
+      // scaling are stored and fenced by now.  One wave-uniform branch per
+      // pass picks the instance, and the fused one is laid out of line (expected not taken): a launch that does not fuse
+      // runs the instruction stream it ran before the fusion existed.  With
+      // the U parts behind branches inside one shared instance those launches
+      // lost 0.2-0.6 ms at C2's shape.
+      if (__builtin_expect(SOCP_FUSE_U && !(SOCP_KO & 4) && a.fuse_u, 0))
+        gemv_G_r<true, true>(xq, S_, H_, DZ);
+      else
+        gemv_G_r<true>(xq, S_, H_, DZ);
       if (lane < nc) {
         if (socl) {
           da = aa < 0.0;
@@ -2704,11 +2736,12 @@ struct Small {
   }
 
   // H (+A'A) -> sweep -> Li;  ALi' = Li A' (n x m);  S = A ALi';  S^-1.
-  __device__ __forceinline__ int factor(bool identity, bool addAA) {
+  __device__ __forceinline__ int factor(int kind, bool addAA) {
+    const bool identity = kind == FAC_IDENT;
     MARK_BEGIN("factor");
     LANE_IDS();
     STAMP(SP_OTHER);
-    if (!identity && !(SOCP_KO & 4)) compute_U();
+    if (kind == FAC_SCALED && !(SOCP_KO & 4)) compute_U();
     STAMP(SP_U);
     form_H(addAA);
     SYNC();
@@ -3040,8 +3073,22 @@ struct Small {
 
   // out[row] = (G u)[row] + add1[row] - add2[row] for rows < k (u in column layout).
   // Rows are reduced over the 16 column lanes in chunks of up to 8 row-steps.
-  template <int P0, int CH, bool NEG = false>
-  __device__ __forceinline__ void gemv_G_chunk(const double (&uq)[NQ], int add1, int add2, int out) {
+  //
+  // FU (the residuals' pass on launches with SmallArgs::fuse_u): the pass also
+  // forms the SYRK's cone rows, U[c,:] = (sum_{i in c} w_i G[i,:]) / (1+wb0),
+  // from the G rows it has taken out of the AGPRs anyway, in compute_U's
+  // operation order (per cone: ascending row steps from 0.0, rows_sum, * CC_I1),
+  // so the same bits.  Every cone is 32 or 64 rows there and starts on a
+  // multiple of its length: a chunk of 8 row steps lies in one cone, a cone is
+  // one chunk or two, and it can only end with a chunk -- one flush site per
+  // chunk.  ua: the accumulators, carried from chunk to chunk.  The chunk's
+  // weights and 1/(1+wb0) are read with its addends (one round trip); a POC
+  // chunk skips the U work by a wave-uniform branch.  The U part stands apart
+  // from the products, after them: a branch per row step cuts the products'
+  // scheduling region into pieces (+0.5 ms at C2).
+  template <int P0, int CH, bool NEG = false, bool FU = false>
+  __device__ __forceinline__ void gemv_G_chunk(const double (&uq)[NQ], int add1, int add2, int out,
+                                               double (&ua)[NQ]) {
     LANE_IDS();
     constexpr int CF = RSCount<CH, 8>::value;
     // the addends of the rows this lane ends up holding, read before the products
@@ -3055,7 +3102,23 @@ struct Small {
         a2[j] = LDS(add2 + row);
       }
     }
+    static_assert(!FU || P0 % 8 == 0, "whole chunks");
+    double uw[FU ? CH : 1], ui = 0.0;
+    bool usoc = false;  // wave-uniform: the chunk's cone is SOC
+    int ucone = 0, upos = 0, ulast = 0;
+    if constexpr (FU && CH == 8) {
+      ulast = a.al_rows == 4;  // a cone is two chunks (64 rows) or one (32)
+      ucone = (P0 / 8) >> ulast;
+      upos = (P0 / 8) & ulast;  // the chunk's place in its cone
+      usoc = (a.fuse_u >> ucone) & 1;
+      if (usoc) {
+#pragma unroll
+        for (int j = 0; j < CH; ++j) uw[j] = LDS(WB + 4 * (P0 + j) + g);
+        ui = LDS(cc(CC_I1, ucone));
+      }
+    }
     double P[CH];
+    double gk[FU ? CH : 1][NQ];  // FU: the chunk's G rows, kept for the U part below
 #pragma unroll
     for (int j = 0; j < CH; ++j) {
       double acc = 0.0;
@@ -3064,8 +3127,33 @@ struct Small {
         a_get_row<NQ>(G[P0 + j], gr);
 #pragma unroll
         for (int q = 0; q < NQ; ++q) acc = fma(gr[q], uq[q], acc);
+        if constexpr (FU) {
+#pragma unroll
+          for (int q = 0; q < NQ; ++q) gk[j][q] = gr[q];
+        }
       }
       P[j] = acc;
+    }
+    if constexpr (FU && CH == 8) {
+      if (usoc) {
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+          double w = uw[j];
+          if (j == 0) w = (g == 0 && upos == 0) ? -(1.0 + w) : w;  // the cone's head row
+#pragma unroll
+          for (int q = 0; q < NQ; ++q) ua[q] = fma(w, gk[j][q], ua[q]);
+        }
+        if (upos == ulast) {  // the cone's last chunk
+#pragma unroll
+          for (int q = 0; q < NQ; ++q) ua[q] = rows_sum(ua[q]);
+          if (g == 0) {
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) LDS(O_U + ucone * NPAD + 16 * q + cl) = ua[q] * ui;
+          }
+#pragma unroll
+          for (int q = 0; q < NQ; ++q) ua[q] = 0.0;
+        }
+      }
     }
     int base = 0;
     rs16<CH, 8>(P, cl, base);
@@ -3081,7 +3169,7 @@ struct Small {
     }
     if constexpr (P0 + CH < NP) {
       constexpr int NXT = (NP - P0 - CH) < 8 ? (NP - P0 - CH) : 8;
-      gemv_G_chunk<P0 + CH, NXT, NEG>(uq, add1, add2, out);
+      gemv_G_chunk<P0 + CH, NXT, NEG, FU>(uq, add1, add2, out, ua);
     }
   }
   __device__ __forceinline__ void gemv_G(int u, int add1, int add2, int out) {
@@ -3090,15 +3178,21 @@ struct Small {
     double uq[NQ];
 #pragma unroll
     for (int q = 0; q < NQ; ++q) uq[q] = LDS(u + 16 * q + cl);
-    gemv_G_chunk<0, (NP < 8 ? NP : 8)>(uq, add1, add2, out);
+    double ua[NQ];  // (FU off: unused)
+    gemv_G_chunk<0, (NP < 8 ? NP : 8)>(uq, add1, add2, out, ua);
     SYNC();
   }
   // the same with u in column layout in registers (uq[q] = u[16q+cl]); NEG:
-  // store the negated rows
-  template <bool NEG = false>
+  // store the negated rows; FU: form U as well where the launch fuses it
+  template <bool NEG = false, bool FU = false>
   __device__ __forceinline__ void gemv_G_r(const double (&uq)[NQ], int add1, int add2, int out) {
     MARK_BEGIN("gemv_G");
-    gemv_G_chunk<0, (NP < 8 ? NP : 8), NEG>(uq, add1, add2, out);
+    double ua[NQ];
+    if constexpr (FU) {
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) ua[q] = 0.0;
+    }
+    gemv_G_chunk<0, (NP < 8 ? NP : 8), NEG, FU>(uq, add1, add2, out, ua);
     SYNC();
   }
 
@@ -3566,7 +3660,8 @@ struct Small {
     int status = ST_MAXIT, iters = 0, it = 0;
     double nd = NAN, np_ = NAN, gap = NAN;
     double ll = 0.0;
-    bool fac_ident = false, fac_aa = false, dm_aa = false;
+    int fac_kind = FAC_SCALED;
+    bool fac_aa = false, dm_aa = false;
     int fret = 0, ret = 0, fst = 0;
     double isc = 1.0;  // DI: the certificate's factor
     int after_singtest;
@@ -3643,7 +3738,7 @@ struct Small {
         case MP_SINGTEST:  // Problem's `sing` (Socp.jl:49-56): is G'G positive definite?
           MARK_BEGIN("case MP_SINGTEST");
           scaling_identity();
-          fac_ident = true;
+          fac_kind = FAC_IDENT;
           fac_aa = false;
           fret = MP_SINGTEST_POST;
           next = MP_FACTOR;
@@ -3655,7 +3750,7 @@ struct Small {
           break;
         case MP_FACTOR:  // setup_iter (densesolver.jl:41-52)
           MARK_BEGIN("case MP_FACTOR");
-          fst = factor(fac_ident, fac_aa);
+          fst = factor(fac_kind, fac_aa);
           if (fst && fret != MP_SINGTEST_POST) {
             status = fst;
             done = true;
@@ -3672,7 +3767,7 @@ struct Small {
             LDS(DS + i) = 0.0;
           }
           SYNC();
-          fac_ident = true;
+          fac_kind = FAC_IDENT;
           fac_aa = sing;
           fret = MP_SOLVE_HEAD;
           ret = RET_INIT;
@@ -3730,7 +3825,8 @@ struct Small {
             }
           }
           // (rmul!(dx, -1) etc., solver.jl:124: the residuals and ds were stored negated)
-          fac_ident = false;
+          // (fused launches: resid_scaling's G x pass has left this scaling's U in LDS)
+          fac_kind = (SOCP_RESID_SCAL && SOCP_FUSE_U && !(SOCP_KO & (2 | 4 | 4096)) && a.fuse_u) ? FAC_SCALED_U : FAC_SCALED;
           fac_aa = sing;
           fret = MP_SOLVE_HEAD;
           ret = RET_AFFINE;
@@ -3745,7 +3841,7 @@ struct Small {
             done = true;
             break;
           }
-          fac_ident = false;
+          fac_kind = FAC_SCALED;
           fac_aa = sing;
           fret = mode == MODE_SETUP ? MP_SAVE : MP_SOLVE_HEAD;
           ret = RET_KKT;
