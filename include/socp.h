@@ -119,6 +119,27 @@ typedef struct socp_params {
  * change of G.  The register kernel's m > 16 shapes, which
  * form the inverse by nature, stay supported. */
 #define SOCP_F_DETECT_INFEASIBLE 256
+/* Parametric batches: one A and one G shared by every problem of the batch
+ * (model-predictive control; the reference's own timed workload solves one
+ * optimal-control problem 100 times with the same matrices, runtests.jl:241-243).
+ * With this flag
+ *   A    points to ONE m x n matrix and G to ONE k x n matrix, column-major
+ *        as above (A[j*m + i], G[j*k + i]);
+ *   sing points to ONE byte, or is NULL for the device probe;
+ * and every problem of the batch uses those.  c, b, h, the iterates and all
+ * outputs stay per problem.  Contract: a call with the flag returns, for every
+ * output array, the bits of the same call without the flag on A, G and sing
+ * replicated B times -- on every kernel and in every combination with the
+ * other flags.  Without the flag nothing changes.  The register kernel then
+ * loads G (and A) once per wavefront instead of once per problem; the other
+ * kernels change only their addressing.
+ * Honoured through params->flags by socp_batch_solve[_ex]; through `flags` by
+ * socp_batch_kkt_solve, socp_dense_create and socp_sqr_create (for all calls
+ * of the handle, socp_sqr_solve_socp included: the handle copies one A and one
+ * G at create, and socp_*_h2d_bytes reports that smaller count; the factor
+ * records stay per problem) and by socp_ingest_create (the matrices are then
+ * given by socp_ingest_set_matrices, not per submit). */
+#define SOCP_F_SHARED_MATRICES 512
 
 typedef struct socp_ctx socp_ctx;
 
@@ -208,7 +229,7 @@ int socp_batch_kkt_solve(socp_ctx* ctx, const socp_dims* dims,
                          const double* s, const double* z,
                          const double* dx, const double* dy, const double* dz, const double* ds,
                          double* cx, double* cy, double* cz, double* cs,
-                         int32_t* kkt_status, int32_t flags);  /* flags: SOCP_F_DEVICE_PTRS | SOCP_F_FORCE_LARGE */
+                         int32_t* kkt_status, int32_t flags);  /* flags: SOCP_F_DEVICE_PTRS | SOCP_F_FORCE_LARGE | SOCP_F_SHARED_MATRICES */
 
 /* The same two methods split the way the reference's KKTSolver plugin is
  * (densesolver.jl): a handle stands for a batch of DenseSolver objects.
@@ -240,7 +261,7 @@ int socp_batch_kkt_solve(socp_ctx* ctx, const socp_dims* dims,
  * flags (at create, for all calls of the handle): SOCP_F_DEVICE_PTRS (every
  * pointer, A and G included, is a device pointer; the calls are then
  * stream-ordered on the context's stream and return without synchronising) |
- * SOCP_F_FORCE_LARGE.  With host pointers each setup_iter moves 2k doubles
+ * SOCP_F_FORCE_LARGE | SOCP_F_SHARED_MATRICES.  With host pointers each setup_iter moves 2k doubles
  * per problem host-to-device and each solve_kkt n+m+2k; A and G move once, at
  * create (socp_dense_h2d_bytes reports the last call's count).  The results are
  * bitwise those of socp_batch_kkt_solve on the same inputs.  Device memory:
@@ -360,7 +381,8 @@ int socp_pack_csc(socp_ctx* ctx, int64_t batch, int32_t rows, int32_t cols,
  * batch i's results drain to pinned memory on a third stream.
  *   socp_ingest_create(ctx, dims, cones..., flags, &ing): dims.batch is the
  *       largest batch one submit may carry (pinned + device space for two
- *       such batches is allocated here); flags: SOCP_F_FORCE_LARGE.
+ *       such batches is allocated here); flags: SOCP_F_FORCE_LARGE |
+ *       SOCP_F_SHARED_MATRICES.
  *   socp_ingest_submit(ing, B, c, A, b, G, h, sing, params, &ticket): host
  *       arrays in the batch layout above, copied into the slot's pinned
  *       block (no copy for arrays already written at the pointers
@@ -376,11 +398,23 @@ int socp_pack_csc(socp_ctx* ctx, int64_t batch, int32_t rows, int32_t cols,
  *       may be NULL).  A CSC batch with bad indices returns SOCP_E_INVALID here.
  * At most two tickets are outstanding: a third submit before the oldest is
  * waited for returns SOCP_E_INVALID.  Results are bitwise those of
- * socp_batch_solve_ex on the same inputs. */
+ * socp_batch_solve_ex on the same inputs.
+ * With SOCP_F_SHARED_MATRICES in socp_ingest_create's flags the slots hold no
+ * A, G or sing staging (the pinned and device blocks shrink accordingly):
+ *   socp_ingest_set_matrices(ing, A, G, sing): the one m x n A, k x n G and
+ *       sing byte (NULL: the device probe) of every later batch.  Host
+ *       pointers; the copy is synchronous.  Allowed only with no ticket
+ *       outstanding (SOCP_E_INVALID otherwise); may be called again between
+ *       batches.  SOCP_E_INVALID on an ingest created without the flag.
+ *   socp_ingest_submit then requires A, G and sing to be NULL and
+ *       set_matrices to have been called (SOCP_E_INVALID otherwise);
+ *       socp_ingest_next_inputs hands back NULL for A, G and sing;
+ *       socp_ingest_submit_csc returns SOCP_E_INVALID. */
 typedef struct socp_ingest socp_ingest;
 int socp_ingest_create(socp_ctx* ctx, const socp_dims* dims,
                        const int32_t* cone_kind, const int32_t* cone_offs, const int32_t* cone_dim,
                        int32_t flags, socp_ingest** out);
+int socp_ingest_set_matrices(socp_ingest* ing, const double* A, const double* G, const uint8_t* sing);
 int socp_ingest_next_inputs(socp_ingest* ing, double** c, double** A, double** b, double** G,
                             double** h, uint8_t** sing);
 int socp_ingest_submit(socp_ingest* ing, int64_t batch, const double* c, const double* A,

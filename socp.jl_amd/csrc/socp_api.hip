@@ -525,8 +525,9 @@ static int dump_problems(socp_ctx* ctx, const SmallArgs& a) {
     double* b = c + n;
     double* h = b + m;
     double* iv = h + k;
-    HIPCHK(hipMemcpy(G, a.G + p * (int64_t)k * n, sizeof(double) * k * n, hipMemcpyDefault));
-    if (m) HIPCHK(hipMemcpy(A, a.A + p * (int64_t)m * n, sizeof(double) * m * n, hipMemcpyDefault));
+    const int64_t pm = (a.flags & SOCP_F_SHARED_MATRICES) ? 0 : p;  // the batch's one A and G
+    HIPCHK(hipMemcpy(G, a.G + pm * (int64_t)k * n, sizeof(double) * k * n, hipMemcpyDefault));
+    if (m) HIPCHK(hipMemcpy(A, a.A + pm * (int64_t)m * n, sizeof(double) * m * n, hipMemcpyDefault));
     HIPCHK(hipMemcpy(c, a.c + p * n, sizeof(double) * n, hipMemcpyDefault));
     if (m) HIPCHK(hipMemcpy(b, a.b + p * m, sizeof(double) * m, hipMemcpyDefault));
     HIPCHK(hipMemcpy(h, a.h + p * k, sizeof(double) * k, hipMemcpyDefault));
@@ -579,6 +580,8 @@ extern "C" int socp_batch_solve_ex(socp_ctx* ctx, const socp_dims* dims, const i
   HIPCHK(hipSetDevice(ctx->device));
   const bool dev = (P.flags & SOCP_F_DEVICE_PTRS) != 0;
   const bool warm = (P.flags & SOCP_F_WARM_START) != 0;
+  // SOCP_F_SHARED_MATRICES: one A, one G and one sing byte for the whole batch
+  const size_t MB = (P.flags & SOCP_F_SHARED_MATRICES) ? 1 : (size_t)B;
   a.B = B;
   a.n = n;
   a.m = m;
@@ -595,11 +598,11 @@ extern "C" int socp_batch_solve_ex(socp_ctx* ctx, const socp_dims* dims, const i
   if (P.flags & SOCP_F_DETECT_INFEASIBLE) small_set_itol(a, ctx->itol);
   typedef socp_ctx X;
   TRY(stage_in(ctx, X::B_C, c, (size_t)B * n, dev, &a.c));
-  TRY(stage_in(ctx, X::B_A, A, (size_t)B * m * n, dev, &a.A));
+  TRY(stage_in(ctx, X::B_A, A, MB * m * n, dev, &a.A));
   TRY(stage_in(ctx, X::B_B, b, (size_t)B * m, dev, &a.b));
-  TRY(stage_in(ctx, X::B_G, G, (size_t)B * k * n, dev, &a.G));
+  TRY(stage_in(ctx, X::B_G, G, MB * k * n, dev, &a.G));
   TRY(stage_in(ctx, X::B_H, h, (size_t)B * k, dev, &a.h));
-  TRY(stage_in(ctx, X::B_SING, sing, (size_t)B, dev, &a.sing));
+  TRY(stage_in(ctx, X::B_SING, sing, MB, dev, &a.sing));
   TRY(stage_out(ctx, X::B_X, x, (size_t)B * n, dev, warm, &a.x));
   TRY(stage_out(ctx, X::B_Y, y, (size_t)B * m, dev, warm, &a.y));
   TRY(stage_out(ctx, X::B_Z, z, (size_t)B * k, dev, warm, &a.z));
@@ -676,13 +679,14 @@ extern "C" int socp_batch_kkt_solve(socp_ctx* ctx, const socp_dims* dims, const 
     return fail(SOCP_E_UNSUPPORTED, kUnsupported);
   HIPCHK(hipSetDevice(ctx->device));
   const bool dev = (flags & SOCP_F_DEVICE_PTRS) != 0;
+  const size_t MB = (flags & SOCP_F_SHARED_MATRICES) ? 1 : (size_t)B;
   a.B = B;
   a.n = n;
   a.m = m;
   a.k = k;
   a.nc = dims->ncones;
   a.mode = MODE_KKT;
-  a.flags = flags & SOCP_F_EXPLICIT_INVERSE;
+  a.flags = flags & (SOCP_F_EXPLICIT_INVERSE | SOCP_F_SHARED_MATRICES);
   a.deg = degree;
   a.dbg = g_kkt_debug;
   a.maxit = 1;
@@ -694,9 +698,9 @@ extern "C" int socp_batch_kkt_solve(socp_ctx* ctx, const socp_dims* dims, const 
   a.c = (const double*)ctx->buf[X::B_C].p;
   a.b = a.c + (size_t)B * n;
   a.h = a.b + (size_t)B * m;
-  TRY(stage_in(ctx, X::B_A, A, (size_t)B * m * n, dev, &a.A));
-  TRY(stage_in(ctx, X::B_G, G, (size_t)B * k * n, dev, &a.G));
-  TRY(stage_in(ctx, X::B_SING, sing, (size_t)B, dev, &a.sing));
+  TRY(stage_in(ctx, X::B_A, A, MB * m * n, dev, &a.A));
+  TRY(stage_in(ctx, X::B_G, G, MB * k * n, dev, &a.G));
+  TRY(stage_in(ctx, X::B_SING, sing, MB, dev, &a.sing));
   TRY(stage_out(ctx, X::B_S, const_cast<double*>(s), (size_t)B * k, dev, true, &a.s));
   TRY(stage_out(ctx, X::B_Z, const_cast<double*>(z), (size_t)B * k, dev, true, &a.z));
   TRY(stage_in(ctx, X::B_DX, dx, (size_t)B * n, dev, &a.dx));
@@ -812,11 +816,12 @@ extern "C" int socp_dense_create(socp_ctx* ctx, const socp_dims* dims, const int
   a.deg = degree;
   a.maxit = 1;
   a.sigma_exp = 3;
-  a.flags = flags & (SOCP_F_DEVICE_PTRS | SOCP_F_EXPLICIT_INVERSE);
+  a.flags = flags & (SOCP_F_DEVICE_PTRS | SOCP_F_EXPLICIT_INVERSE | SOCP_F_SHARED_MATRICES);
   if (B == 0) {
     *out = h;
     return 0;
   }
+  const size_t MB = (flags & SOCP_F_SHARED_MATRICES) ? 1 : (size_t)B;  // one A, G, sing for the batch
   typedef socp_dense D;
   // the handle owns its copies (the caller's device buffers may be reused)
   auto own = [&](int slot, const void* src, size_t bytes) -> int {
@@ -827,9 +832,9 @@ extern "C" int socp_dense_create(socp_ctx* ctx, const socp_dims* dims, const int
     if (!dev) h->h2d_bytes += (int64_t)bytes;
     return 0;
   };
-  if ((rc = own(D::D_A, A, (size_t)B * m * n * sizeof(double)))) return bail(rc);
-  if ((rc = own(D::D_G, G, (size_t)B * k * n * sizeof(double)))) return bail(rc);
-  if ((rc = own(D::D_SING, sing, (size_t)B))) return bail(rc);
+  if ((rc = own(D::D_A, A, MB * m * n * sizeof(double)))) return bail(rc);
+  if ((rc = own(D::D_G, G, MB * k * n * sizeof(double)))) return bail(rc);
+  if ((rc = own(D::D_SING, sing, MB))) return bail(rc);
   a.A = m > 0 ? (const double*)h->buf[D::D_A].p : nullptr;
   a.G = (const double*)h->buf[D::D_G].p;
   a.sing = sing ? (const uint8_t*)h->buf[D::D_SING].p : nullptr;
@@ -1022,6 +1027,8 @@ extern "C" int socp_sqr_create(socp_ctx* ctx, const socp_dims* dims, const int32
   if (B > 0 && (!G || (m > 0 && !A))) return bail(fail(SOCP_E_INVALID, "NULL data pointer"));
   if (hipSetDevice(ctx->device) != hipSuccess) return bail(fail(SOCP_E_HIP, "hipSetDevice"));
   h->dev = (flags & SOCP_F_DEVICE_PTRS) != 0;
+  a.shared = (flags & SOCP_F_SHARED_MATRICES) ? 1 : 0;
+  const size_t MB = a.shared ? 1 : (size_t)B;  // one A, G, sing for the batch
   a.B = B;
   a.n = n;
   a.m = m;
@@ -1041,9 +1048,9 @@ extern "C" int socp_sqr_create(socp_ctx* ctx, const socp_dims* dims, const int32
     if (!h->dev) h->h2d_bytes += (int64_t)bytes;
     return 0;
   };
-  if ((rc = own(Q::Q_A, A, (size_t)B * m * n * sizeof(double)))) return bail(rc);
-  if ((rc = own(Q::Q_G, G, (size_t)B * k * n * sizeof(double)))) return bail(rc);
-  if ((rc = own(Q::Q_SING, sing, (size_t)B))) return bail(rc);
+  if ((rc = own(Q::Q_A, A, MB * m * n * sizeof(double)))) return bail(rc);
+  if ((rc = own(Q::Q_G, G, MB * k * n * sizeof(double)))) return bail(rc);
+  if ((rc = own(Q::Q_SING, sing, MB))) return bail(rc);
   a.A = m > 0 ? (const double*)h->buf[Q::Q_A].p : nullptr;
   a.G = (const double*)h->buf[Q::Q_G].p;
   a.sing = sing ? (const uint8_t*)h->buf[Q::Q_SING].p : nullptr;
@@ -1191,7 +1198,7 @@ extern "C" int socp_sqr_solve_socp(socp_sqr* h, const double* c, const double* b
   memset(&ia, 0, sizeof(ia));
   ia.B = B; ia.n = n; ia.m = m; ia.k = k; ia.nc = h->a.nc; ia.deg = h->deg; ia.sigma_exp = P.sigma_exp;
   ia.cones = h->a.cones;
-  ia.A = h->a.A; ia.G = h->a.G;
+  ia.A = h->a.A; ia.G = h->a.G; ia.shared = h->a.shared;
   double* dc = d;
   double* db = dc + (size_t)B * n;
   double* dh = db + (size_t)B * m;
@@ -1668,21 +1675,27 @@ struct socp_ingest {
   IngestSlot slot[2];
   int64_t next = 0;
   DevBuf counter, err;
+  // SOCP_F_SHARED_MATRICES: the batch's one A, G and sing byte live here
+  // (socp_ingest_set_matrices), not in the slots
+  bool shared = false, have_mat = false, mat_sing = false;
+  DevBuf mat;
 };
 
 // the byte layout of one slot's blocks for `B` problems
 struct InLayout {
   size_t c, A, b, G, h, sing, total;
 };
-static InLayout in_layout(const socp_dims& d, int64_t B) {
+// (shared: a SOCP_F_SHARED_MATRICES ingest stages no A, G or sing per batch)
+static InLayout in_layout(const socp_dims& d, int64_t B, bool shared) {
   InLayout L;
   size_t o = 0;
+  const size_t MB = shared ? 0 : (size_t)B;
   L.c = o;    o += al_up(sizeof(double) * B * d.n);
-  L.A = o;    o += al_up(sizeof(double) * B * d.m * d.n);
+  L.A = o;    o += al_up(sizeof(double) * MB * d.m * d.n);
   L.b = o;    o += al_up(sizeof(double) * B * d.m);
-  L.G = o;    o += al_up(sizeof(double) * B * d.k * d.n);
+  L.G = o;    o += al_up(sizeof(double) * MB * d.k * d.n);
   L.h = o;    o += al_up(sizeof(double) * B * d.k);
-  L.sing = o; o += al_up((size_t)B);
+  L.sing = o; o += al_up(MB);
   L.total = o;
   return L;
 }
@@ -1723,6 +1736,7 @@ static void ingest_free(socp_ingest* g) {
   }
   g->counter.release();
   g->err.release();
+  g->mat.release();
   if (g->h2d) (void)hipStreamDestroy(g->h2d);
   if (g->d2h) (void)hipStreamDestroy(g->d2h);
   delete g;
@@ -1744,6 +1758,7 @@ extern "C" int socp_ingest_create(socp_ctx* ctx, const socp_dims* dims, const in
   if (rc) return bail(rc);
   g->dims = *dims;
   g->flags = flags & SOCP_F_FORCE_LARGE;
+  g->shared = (flags & SOCP_F_SHARED_MATRICES) != 0;
   const int n = dims->n, m = dims->m, k = dims->k;
   g->v = ((flags & SOCP_F_FORCE_LARGE) || dims->ncones > NCS) ? nullptr : pick_variant(n, m, k);
   if (!g->v && !large_fits(n, m, k, dims->ncones, nullptr)) return bail(fail(SOCP_E_UNSUPPORTED, kUnsupported));
@@ -1753,7 +1768,7 @@ extern "C" int socp_ingest_create(socp_ctx* ctx, const socp_dims* dims, const in
       (e = hipStreamCreateWithFlags(&g->d2h, hipStreamNonBlocking)) != hipSuccess)
     return bail(fail(SOCP_E_HIP, std::string("hipStreamCreateWithFlags: ") + hipGetErrorString(e)));
   const int64_t B = dims->batch;
-  const InLayout Li = in_layout(*dims, B);
+  const InLayout Li = in_layout(*dims, B, g->shared);
   const OutLayout Lo = out_layout(*dims, B);
   for (auto& sl : g->slot) {
     if (hipEventCreateWithFlags(&sl.ready, hipEventDisableTiming) != hipSuccess ||
@@ -1769,6 +1784,8 @@ extern "C" int socp_ingest_create(socp_ctx* ctx, const socp_dims* dims, const in
       return bail(fail(SOCP_E_NOMEM, "device allocation failed"));
   }
   if (g->counter.ensure(256) || g->err.ensure(256)) return bail(fail(SOCP_E_NOMEM, "device allocation failed"));
+  if (g->shared && g->mat.ensure(al_up(sizeof(double) * m * n) + al_up(sizeof(double) * k * n) + kAl))
+    return bail(fail(SOCP_E_NOMEM, "device allocation failed"));
   *out = g;
   return 0;
 }
@@ -1785,14 +1802,37 @@ extern "C" int socp_ingest_next_inputs(socp_ingest* g, double** c, double** A, d
   if (!g) return fail(SOCP_E_INVALID, "ingest is NULL");
   IngestSlot& sl = g->slot[g->next & 1];
   if (sl.ticket >= 0) return fail(SOCP_E_INVALID, "the next slot is busy: wait for its ticket first");
-  const InLayout L = in_layout(g->dims, g->dims.batch);
+  const InLayout L = in_layout(g->dims, g->dims.batch, g->shared);
   char* base = (char*)sl.pin_in;
   if (c) *c = (double*)(base + L.c);
-  if (A) *A = (double*)(base + L.A);
+  if (A) *A = g->shared ? nullptr : (double*)(base + L.A);
   if (b) *b = (double*)(base + L.b);
-  if (G) *G = (double*)(base + L.G);
+  if (G) *G = g->shared ? nullptr : (double*)(base + L.G);
   if (h) *h = (double*)(base + L.h);
-  if (sing) *sing = (uint8_t*)(base + L.sing);
+  if (sing) *sing = g->shared ? nullptr : (uint8_t*)(base + L.sing);
+  return 0;
+}
+
+// SOCP_F_SHARED_MATRICES: the one A (m x n), G (k x n) and sing byte (NULL: the
+// device probe) of every later batch.  Host pointers, copied synchronously;
+// only with no ticket outstanding.
+extern "C" int socp_ingest_set_matrices(socp_ingest* g, const double* A, const double* G, const uint8_t* sing) {
+  if (!g) return fail(SOCP_E_INVALID, "ingest is NULL");
+  if (!g->shared) return fail(SOCP_E_INVALID, "the ingest was created without SOCP_F_SHARED_MATRICES");
+  for (auto& sl : g->slot)
+    if (sl.ticket >= 0) return fail(SOCP_E_INVALID, "a ticket is outstanding: wait for it before set_matrices");
+  const socp_dims& d = g->dims;
+  if (!G || (d.m > 0 && !A)) return fail(SOCP_E_INVALID, "NULL data pointer");
+  HIPCHK(hipSetDevice(g->ctx->device));
+  const size_t bA = sizeof(double) * d.m * d.n, bG = sizeof(double) * d.k * d.n;
+  char* dm = (char*)g->mat.p;
+  hipStream_t st = g->ctx->stream;
+  if (bA) HIPCHK(hipMemcpyAsync(dm, A, bA, hipMemcpyHostToDevice, st));
+  if (bG) HIPCHK(hipMemcpyAsync(dm + al_up(bA), G, bG, hipMemcpyHostToDevice, st));
+  if (sing) HIPCHK(hipMemcpyAsync(dm + al_up(bA) + al_up(bG), sing, 1, hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  g->mat_sing = sing != nullptr;
+  g->have_mat = true;
   return 0;
 }
 
@@ -1802,7 +1842,7 @@ static int ingest_solve(socp_ingest* g, IngestSlot& sl, int64_t B, const uint8_t
                         const socp_params* params, const double* A_dev, const double* G_dev) {
   socp_ctx* ctx = g->ctx;
   const socp_dims& d = g->dims;
-  const InLayout Li = in_layout(d, d.batch);
+  const InLayout Li = in_layout(d, d.batch, g->shared);
   const OutLayout Lo = out_layout(d, d.batch);
   char* din = (char*)sl.dev_in.p;
   char* dout = (char*)sl.dev_out.p;
@@ -1824,7 +1864,8 @@ static int ingest_solve(socp_ingest* g, IngestSlot& sl, int64_t B, const uint8_t
   a.tol = P.tol;
   a.step = P.step;
   a.init_eps = P.init_eps;
-  a.flags = P.flags & ~SOCP_F_WARM_START;
+  // (whether the matrices are shared is the ingest's property, not the submit's)
+  a.flags = (P.flags & ~(SOCP_F_WARM_START | SOCP_F_SHARED_MATRICES)) | (g->shared ? SOCP_F_SHARED_MATRICES : 0);
   a.mode = MODE_SOLVE;
   a.deg = g->degree;
   if (P.flags & SOCP_F_DETECT_INFEASIBLE) small_set_itol(a, ctx->itol);
@@ -1873,11 +1914,19 @@ extern "C" int socp_ingest_submit(socp_ingest* g, int64_t batch, const double* c
   const socp_dims& d = g->dims;
   const int64_t B = batch;
   if (!ticket) return fail(SOCP_E_INVALID, "ticket is NULL");
-  if (B > 0 && (!c || !G || !h || (d.m > 0 && (!A || !b)))) return fail(SOCP_E_INVALID, "NULL data pointer");
-  const InLayout L = in_layout(d, d.batch);
+  if (g->shared) {
+    if (A || G || sing)
+      return fail(SOCP_E_INVALID, "shared ingest: A, G and sing must be NULL (socp_ingest_set_matrices gives them)");
+    if (!g->have_mat) return fail(SOCP_E_INVALID, "shared ingest: socp_ingest_set_matrices has not been called");
+    if (B > 0 && (!c || !h || (d.m > 0 && !b))) return fail(SOCP_E_INVALID, "NULL data pointer");
+  } else if (B > 0 && (!c || !G || !h || (d.m > 0 && (!A || !b)))) {
+    return fail(SOCP_E_INVALID, "NULL data pointer");
+  }
+  const InLayout L = in_layout(d, d.batch, g->shared);
   char* pin = (char*)sl.pin_in;
   char* din = (char*)sl.dev_in.p;
   // host -> pinned (skipped for arrays already written into the slot)
+  // (a shared ingest's A, G and sing are NULL here: skipped below)
   const size_t nb[6] = {sizeof(double) * B * d.n, sizeof(double) * B * d.m * d.n, sizeof(double) * B * d.m,
                         sizeof(double) * B * d.k * d.n, sizeof(double) * B * d.k, (size_t)B};
   const size_t off[6] = {L.c, L.A, L.b, L.G, L.h, L.sing};
@@ -1887,9 +1936,15 @@ extern "C" int socp_ingest_submit(socp_ingest* g, int64_t batch, const double* c
   for (int i = 0; i < 6; ++i)
     if (src[i] && nb[i]) HIPCHK(hipMemcpyAsync(din + off[i], pin + off[i], nb[i], hipMemcpyHostToDevice, g->h2d));
   HIPCHK(hipEventRecord(sl.ready, g->h2d));
-  if (B > 0)
+  if (B > 0 && g->shared) {
+    const char* dm = (const char*)g->mat.p;
+    const size_t oG = al_up(sizeof(double) * d.m * d.n), oS = oG + al_up(sizeof(double) * d.k * d.n);
+    TRY(ingest_solve(g, sl, B, (const uint8_t*)(dm + oS), g->mat_sing, params, (const double*)dm,
+                     (const double*)(dm + oG)));
+  } else if (B > 0) {
     TRY(ingest_solve(g, sl, B, (const uint8_t*)(din + L.sing), sing != nullptr, params,
                      (const double*)(din + L.A), (const double*)(din + L.G)));
+  }
   sl.ticket = g->next++;
   sl.batch = B;
   sl.csc = false;
@@ -1906,6 +1961,7 @@ extern "C" int socp_ingest_submit_csc(socp_ingest* g, int64_t batch, const doubl
                                       const double* G_nzval, int32_t index_base, const socp_params* params,
                                       int64_t* ticket) {
   if (params) TRY(check_detect_flags(params->flags));
+  if (g && g->shared) return fail(SOCP_E_INVALID, "socp_ingest_submit_csc on a SOCP_F_SHARED_MATRICES ingest");
   IngestSlot* slp = nullptr;
   TRY(ingest_begin(g, batch, &slp));
   IngestSlot& sl = *slp;
@@ -1915,7 +1971,7 @@ extern "C" int socp_ingest_submit_csc(socp_ingest* g, int64_t batch, const doubl
   if (index_base != 0 && index_base != 1) return fail(SOCP_E_INVALID, "index_base must be 0 or 1");
   if (B > 0 && (!c || !h || !G_nz_offs || !G_colptr || (d.m > 0 && (!b || !A_nz_offs || !A_colptr))))
     return fail(SOCP_E_INVALID, "NULL data pointer");
-  const InLayout L = in_layout(d, d.batch);
+  const InLayout L = in_layout(d, d.batch, g->shared);
   char* pin = (char*)sl.pin_in;
   char* din = (char*)sl.dev_in.p;
   const size_t nb[4] = {sizeof(double) * B * d.n, sizeof(double) * B * d.m, sizeof(double) * B * d.k, (size_t)B};

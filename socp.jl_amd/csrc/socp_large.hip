@@ -356,7 +356,9 @@ struct Large {
   }
 
   __device__ void load(int64_t p) {
-    Gp = (gcdbl*)a.G + p * (int64_t)k * n;
+    // SOCP_F_SHARED_MATRICES: every problem reads the batch's one A, G and sing
+    const int64_t pm = (a.flags & F_SHARED) ? 0 : p;
+    Gp = (gcdbl*)a.G + pm * (int64_t)k * n;
     for (int e = tid; e < 7 * L.KP; e += NTH) LV(L.o_kvd + e) = 0.0;
     for (int e = tid; e < 8 * L.KP; e += NTH) LV(L.o_kvl + e) = 0.0;
     for (int e = tid; e < 6 * L.NPAD + 5 * L.MPAD; e += NTH) LV(L.o_nv + e) = 0.0;
@@ -364,7 +366,7 @@ struct Large {
     for (int j = tid; j < n; j += NTH) LV(C_ + j) = a.c[p * n + j];
     for (int i = tid; i < m; i += NTH) LV(B_ + i) = a.b[p * m + i];
     for (int i = tid; i < k; i += NTH) LV(H_ + i) = a.h[p * k + i];
-    const double* Ag = a.A + p * (int64_t)m * n;
+    const double* Ag = a.A + pm * (int64_t)m * n;
     const int NP = L.NPAD, MP = L.MPAD;
     for (int e = tid; e < MP * NP; e += NTH) {
       const int j = e / MP, r = e - j * MP;
@@ -2667,7 +2669,7 @@ struct Large {
       return;
     }
     if (a.sing) {
-      sing = a.sing[p] != 0;
+      sing = a.sing[(a.flags & F_SHARED) ? 0 : p] != 0;
     } else {  // Problem's `sing` (Socp.jl:49-56): does cholesky(G'G) fail?
       scaling_identity();
       sing = factor(false, true) == ST_CHOL_H;

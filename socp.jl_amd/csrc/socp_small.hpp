@@ -49,7 +49,7 @@ struct ConeTable {
 // record; solve_kkt :54-90 solves one right-hand side against it)
 enum { MODE_SOLVE = 0, MODE_KKT = 1, MODE_SETUP = 2, MODE_SOLVEKKT = 3 };
 enum { ST_CONVERGED = 0, ST_MAXIT = 1, ST_CHOL_H = 2, ST_CHOL_S = 3, ST_DOMAIN = 4, ST_PRIMAL_INF = 5, ST_DUAL_INF = 6 };
-enum { F_WARM = 2, F_DETECT = 256 };
+enum { F_WARM = 2, F_DETECT = 256, F_SHARED = 512 };
 
 // SOCP_F_DETECT_INFEASIBLE (include/socp.h): the verdict from the five sums
 // hz = h'z + b'y, |A'y + G'z|^2, cx = c'x, |Ax|^2, |Gx + s|^2 of the iterate.
@@ -337,6 +337,37 @@ __device__ __forceinline__ void a_put(AD& r, double v) {
   const uint64_t u = (uint64_t)__double_as_longlong(v);
   asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(r.lo) : "v"((uint32_t)u));
   asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(r.hi) : "v"((uint32_t)(u >> 32)));
+}
+// a_put in the lanes of `mask` only (EXEC narrowed inside the statement): the
+// other lanes keep what they hold.  With mask = 0 the AGPRs are carried over
+// unchanged without a branch around the statement -- the values then live
+// across the problem loop as tied operands, which the register allocator keeps
+// in place (a conditional a_put makes them phi nodes instead, and clang-22's
+// AGPR-copy rewrite has crashed on those).
+__device__ __forceinline__ void a_put_masked(AD& r, uint64_t u, uint64_t mask) {
+  uint64_t sv;
+  asm volatile(
+      "s_and_saveexec_b64 %2, %5\n\tv_accvgpr_write_b32 %0, %3\n\tv_accvgpr_write_b32 %1, %4\n\t"
+      "s_mov_b64 exec, %2"
+      : "+a"(r.lo), "+a"(r.hi), "=&s"(sv)
+      : "v"((uint32_t)u), "v"((uint32_t)(u >> 32)), "s"(mask)
+      : "scc");
+}
+__device__ __forceinline__ void a_put4_masked(AD& r0, AD& r1, AD& r2, AD& r3, uint64_t u0, uint64_t u1, uint64_t u2,
+                                              uint64_t u3, uint64_t mask) {
+  uint64_t sv;
+  asm volatile(
+      "s_and_saveexec_b64 %8, %17\n\t"
+      "v_accvgpr_write_b32 %0, %9\n\tv_accvgpr_write_b32 %1, %10\n\t"
+      "v_accvgpr_write_b32 %2, %11\n\tv_accvgpr_write_b32 %3, %12\n\t"
+      "v_accvgpr_write_b32 %4, %13\n\tv_accvgpr_write_b32 %5, %14\n\t"
+      "v_accvgpr_write_b32 %6, %15\n\tv_accvgpr_write_b32 %7, %16\n\t"
+      "s_mov_b64 exec, %8"
+      : "+a"(r0.lo), "+a"(r0.hi), "+a"(r1.lo), "+a"(r1.hi), "+a"(r2.lo), "+a"(r2.hi), "+a"(r3.lo), "+a"(r3.hi),
+        "=&s"(sv)
+      : "v"((uint32_t)u0), "v"((uint32_t)(u0 >> 32)), "v"((uint32_t)u1), "v"((uint32_t)(u1 >> 32)),
+        "v"((uint32_t)u2), "v"((uint32_t)(u2 >> 32)), "v"((uint32_t)u3), "v"((uint32_t)(u3 >> 32)), "s"(mask)
+      : "scc");
 }
 __device__ __forceinline__ double a_get(const AD& r) {
   uint32_t lo, hi;
@@ -1045,6 +1076,21 @@ struct Small {
   }
 
   bool ko_gloaded = false;
+#ifndef SOCP_SHARED_RESIDENT
+#define SOCP_SHARED_RESIDENT 3  // bit 0: G stays resident, bit 1: A; 0: SOCP_F_SHARED_MATRICES changes the addressing only (A/B builds)
+#endif
+  // SOCP_F_SHARED_MATRICES: G (AGPRs) and A (LDS block O_A) hold the batch's
+  // one G and A since this wave's first problem.  Nothing else writes them:
+  // G's AGPRs are written in load_problem alone, O_A is only read after it.
+  // A later problem's load_problem keeps its control flow: G's buffer
+  // descriptor gets an empty range (every load returns 0 without touching
+  // memory) and the AGPR writes run with no lane enabled (a_put_masked).
+  // The m > 32 variants (MQ = 4) keep neither: with G's AGPRs live across the
+  // problem loop clang-22 crashes on several of them (the MFMA_FORM fallback of
+  // the Makefile would then change how they are built); they change only
+  // their addressing and reload the shared G and A per problem, from L2.
+  static constexpr bool RES_G = (SOCP_SHARED_RESIDENT & 1) && MQ < 4, RES_A = (SOCP_SHARED_RESIDENT & 2) && MQ < 4;
+  bool mat_resident = false;
   // lane c < nc: its cone's kind and offset (per-cone work without the table
   // round trips)
   bool lc_soc = false;
@@ -1052,15 +1098,18 @@ struct Small {
   __device__ __forceinline__ void load_problem(int64_t p) {
     MARK_BEGIN("load_problem");
     LANE_IDS();
-    const double* Gp = a.G + p * (int64_t)k * n;
+    const bool shared = (a.flags & F_SHARED) != 0;
+    const bool keep = SOCP_SHARED_RESIDENT && shared && mat_resident;  // wave-uniform
+    const bool keep_g = RES_G && keep, keep_a = RES_A && keep;
+    const double* Gp = a.G + (shared ? 0 : p * (int64_t)k * n);
     // the vectors and the first chunk of A are requested first: their HBM
     // round trip runs under G's (n, m <= 64 here, k <= 128)
     const double cv = lane < n ? a.c[p * n + lane] : 0.0;
     const double bv = lane < m ? a.b[p * m + lane] : 0.0;
     const double hv0 = lane < k ? a.h[p * k + lane] : 0.0;
     const double hv1 = lane + 64 < k ? a.h[p * k + 64 + lane] : 0.0;
-    const double* Ap = a.A + p * (int64_t)m * n;
-    const int mn = m * n;
+    const double* Ap = a.A + (shared ? 0 : p * (int64_t)m * n);
+    const int mn = keep_a ? 0 : m * n;  // a resident A is neither loaded nor stored again
     constexpr int AB = HOIST_CST ? 16 : 8;
     double av[AB];
 #pragma unroll
@@ -1083,7 +1132,10 @@ struct Small {
     const uint64_t gbase = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(gpu >> 32)) << 32) |
                            (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)gpu);
     const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)gbase, (short)0, __builtin_amdgcn_readfirstlane(k * n * (int)sizeof(double)), 0x00020000);
+        (void*)gbase, (short)0, __builtin_amdgcn_readfirstlane(keep_g ? 0 : k * n * (int)sizeof(double)), 0x00020000);
+    // lanes that take the loaded G (all or none; made wave-uniform explicitly: the statement wants SGPRs)
+    const uint32_t wm = (uint32_t)__builtin_amdgcn_readfirstlane(keep_g ? 0 : -1);
+    const uint64_t wmask = ((uint64_t)wm << 32) | wm;
     int colk[NQ];  // byte offset of the lane's column in each column tile, or "out of range"
 #pragma unroll
     for (int q = 0; q < NQ; ++q) colk[q] = 16 * q + cl < n ? (16 * q + cl) * k * 8 : 0x40000000;
@@ -1100,15 +1152,32 @@ struct Small {
           tmp[t] = __builtin_bit_cast(uint64_t, __builtin_amdgcn_raw_buffer_load_b64(grs, off, 0, 0));
         }
       }
+      if constexpr (!RES_G) {
 #pragma unroll
-      for (int t = 0; t < GB; ++t) {
-        const int e = b0 + t;
-        if (e < GT) a_put(G[e / NQ][e % NQ], __longlong_as_double((long long)tmp[t]));
+        for (int t = 0; t < GB; ++t) {
+          const int e = b0 + t;
+          if (e < GT) a_put(G[e / NQ][e % NQ], __longlong_as_double((long long)tmp[t]));
+        }
+      } else {
+#pragma unroll
+        for (int t = 0; t < GB; t += 4) {
+          const int e = b0 + t;
+          if (e + 3 < GT) {
+            a_put4_masked(G[e / NQ][e % NQ], G[(e + 1) / NQ][(e + 1) % NQ], G[(e + 2) / NQ][(e + 2) % NQ],
+                          G[(e + 3) / NQ][(e + 3) % NQ], tmp[t], tmp[t + 1], tmp[t + 2], tmp[t + 3], wmask);
+          } else {
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+              if (e + u < GT) a_put_masked(G[(e + u) / NQ][(e + u) % NQ], tmp[t + u], wmask);
+          }
+        }
       }
     }
     }
     for (int e = lane; e < NKV * SH::KS; e += 64) LDS(O_KV + e) = 0.0;
-    for (int e = lane; e < O_U + SH::UAL - O_A; e += 64) LDS(O_A + e) = 0.0;
+    // (a resident A keeps its block, padding zeros included: the fill starts behind it)
+    for (int e = lane + (keep_a ? MPAD * LDA : 0); e < O_U + SH::UAL - O_A; e += 64) LDS(O_A + e) = 0.0;
+    mat_resident = shared;
     SYNC();
     if (lane < n) LDS(C_ + lane) = cv;
     if (lane < m) LDS(B_ + lane) = bv;
@@ -3717,7 +3786,7 @@ struct Small {
     if (have_sing) {
       phase = after_singtest;
     } else if (a.sing) {
-      sing = uni((int)a.sing[p]) != 0;
+      sing = uni((int)a.sing[(a.flags & F_SHARED) ? 0 : p]) != 0;
       phase = after_singtest;
     } else {
       sing = false;

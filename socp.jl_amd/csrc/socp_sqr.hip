@@ -332,9 +332,10 @@ __device__ __forceinline__ void setup_problem(Ctx& C, int64_t p) {
   double* lds = C.lds;
   const int lane = C.lane;
   const int n = a.n, m = a.m, k = a.k, nc = a.nc;
-  const double* G = a.G + p * (int64_t)k * n;
-  const double* A = m ? a.A + p * (int64_t)m * n : nullptr;
-  const bool sing = a.sing && a.sing[p];
+  const int64_t pm = a.shared ? 0 : p;  // SOCP_F_SHARED_MATRICES: the batch's one A, G and sing
+  const double* G = a.G + pm * (int64_t)k * n;
+  const double* A = m ? a.A + pm * (int64_t)m * n : nullptr;
+  const bool sing = a.sing && a.sing[pm];
   double* rec = a.rec + p * L.rec;
   if (a.active && !a.active[p]) return;
 #ifdef SOCP_DIAG
@@ -793,9 +794,10 @@ __device__ __forceinline__ void solve_problem(Ctx& C, int64_t p) {
   double* lds = C.lds;
   const int lane = C.lane;
   const int n = a.n, m = a.m, k = a.k, nc = a.nc;
-  const double* G = a.G + p * (int64_t)k * n;
-  const double* A = m ? a.A + p * (int64_t)m * n : nullptr;
-  const bool sing = a.sing && a.sing[p];
+  const int64_t pm = a.shared ? 0 : p;  // SOCP_F_SHARED_MATRICES: the batch's one A, G and sing
+  const double* G = a.G + pm * (int64_t)k * n;
+  const double* A = m ? a.A + pm * (int64_t)m * n : nullptr;
+  const bool sing = a.sing && a.sing[pm];
   const double* rec = a.rec + p * L.rec;
   if (a.active && !a.active[p]) return;
   const int status = (int)rec[L.r_st];
@@ -1033,9 +1035,10 @@ __device__ __forceinline__ void setup_problem_wg(Ctx& C, int64_t p, int tid) {
   const SqrLayout& L = C.L;
   double* lds = C.lds;
   const int n = a.n, m = a.m, k = a.k, nc = a.nc;
-  const double* G = a.G + p * (int64_t)k * n;
-  const double* A = m ? a.A + p * (int64_t)m * n : nullptr;
-  const bool sing = a.sing && a.sing[p];
+  const int64_t pm = a.shared ? 0 : p;  // SOCP_F_SHARED_MATRICES: the batch's one A, G and sing
+  const double* G = a.G + pm * (int64_t)k * n;
+  const double* A = m ? a.A + pm * (int64_t)m * n : nullptr;
+  const bool sing = a.sing && a.sing[pm];
   double* rec = a.rec + p * L.rec;
   if (a.active && !a.active[p]) return;  // uniform over the workgroup
   double* P = L.gfac ? rec + L.r_P : lds + L.o_L;  // the packed factor of H
@@ -1191,9 +1194,10 @@ __device__ __forceinline__ void solve_problem_wg(Ctx& C, int64_t p, int tid) {
   const SqrLayout& L = C.L;
   double* lds = C.lds;
   const int n = a.n, m = a.m, k = a.k, nc = a.nc;
-  const double* G = a.G + p * (int64_t)k * n;
-  const double* A = m ? a.A + p * (int64_t)m * n : nullptr;
-  const bool sing = a.sing && a.sing[p];
+  const int64_t pm = a.shared ? 0 : p;  // SOCP_F_SHARED_MATRICES: the batch's one A, G and sing
+  const double* G = a.G + pm * (int64_t)k * n;
+  const double* A = m ? a.A + pm * (int64_t)m * n : nullptr;
+  const bool sing = a.sing && a.sing[pm];
   const double* rec = a.rec + p * L.rec;
   if (a.active && !a.active[p]) return;  // uniform over the workgroup
   const int status = (int)rec[L.r_st];

@@ -136,6 +136,7 @@ struct SqrArgs {
   int32_t detect;
   double itol;
   double *ux, *uy, *uz, *us;
+  int32_t shared;  // SOCP_F_SHARED_MATRICES: A, G and sing are the batch's one (offset 0 for every problem)
 };
 
 // the batched solve_socp on the rank-update plugin (socp_sqr_ipm.hip): the
@@ -154,6 +155,7 @@ struct SqrIpmArgs {
   double tol, step, init_eps;
   int32_t detect;  // SOCP_F_DETECT_INFEASIBLE: the rule follows the exit test
   double itol;     // its tolerance
+  int32_t shared;  // SOCP_F_SHARED_MATRICES: A and G are the batch's one
 };
 size_t sqr_ipm_lds_bytes(int n, int m, int k);
 // The wavefront solve kernel reads no H-product chunk buffers: with

@@ -55,8 +55,9 @@ __device__ double max_step_w(const ConeTable& C, const double* x, int lane) {
 __device__ void residuals_w(const SqrIpmArgs& a, int64_t p, double* rdv, double* rpv, double* rzv, double (&r3)[3],
                             int lane) {
   const int n = a.n, m = a.m, k = a.k;
-  const double* G = a.G + p * (int64_t)k * n;
-  const double* A = m ? a.A + p * (int64_t)m * n : nullptr;
+  const int64_t pm = a.shared ? 0 : p;  // SOCP_F_SHARED_MATRICES: the batch's one A and G
+  const double* G = a.G + pm * (int64_t)k * n;
+  const double* A = m ? a.A + pm * (int64_t)m * n : nullptr;
   const double *x = a.x + p * n, *y = a.y + p * m, *z = a.z + p * k, *s = a.s + p * k;
   const int cl = lane & 15;
   if (k > 256 || m > 256) {

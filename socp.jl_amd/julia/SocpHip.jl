@@ -28,6 +28,9 @@ const SOCP_F_EXPLICIT_INVERSE = Int32(8)   # Li = H^-1 formed, the reference's o
 # state; not together with SOCP_F_EXPLICIT_INVERSE.  Like the rest of this
 # file, these additions have not been executed here (no Julia in the image).
 const SOCP_F_DETECT_INFEASIBLE = Int32(256)
+# One A, one G and one sing byte for every problem of the batch (parametric
+# batches); the outputs are bitwise those of the replicated call (include/socp.h)
+const SOCP_F_SHARED_MATRICES = Int32(512)
 const SOCP_PRIMAL_INFEASIBLE = Int32(5)
 const SOCP_DUAL_INFEASIBLE = Int32(6)
 "tau of the detection rule for every later solve of this process's context (default 1e-7)."
@@ -161,7 +164,9 @@ mutable struct HipDenseSolver <: KKTSolver{HipScaling}
     handle::Ptr{Cvoid}
     status::Vector{Int32}
     # explicit_inverse=true: SOCP_F_EXPLICIT_INVERSE, Li = H^-1 formed as densesolver.jl:48 does
-    function HipDenseSolver(pr::Problem{C,n,m,k,sing}; explicit_inverse::Bool=false) where {C,n,m,k,sing}
+    # shared_matrices=true: SOCP_F_SHARED_MATRICES (this handle's batch is one problem: the same result)
+    function HipDenseSolver(pr::Problem{C,n,m,k,sing}; explicit_inverse::Bool=false,
+                            shared_matrices::Bool=false) where {C,n,m,k,sing}
         kind, offs, dim = cone_arrays(pr.cones)
         dims = Ref(SocpDims(1, n, m, k, length(pr.cones)))
         A = Matrix{Float64}(pr.A)   # column-major m x n, as include/socp.h lays it out
@@ -172,7 +177,8 @@ mutable struct HipDenseSolver <: KKTSolver{HipScaling}
                          (Ptr{Cvoid}, Ref{SocpDims}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32},
                           Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Int32, Ptr{Ptr{Cvoid}}),
                          socp_ctx(), dims, kind, offs, dim, A, G, singv,
-                         explicit_inverse ? SOCP_F_EXPLICIT_INVERSE : Int32(0), h))
+                         (explicit_inverse ? SOCP_F_EXPLICIT_INVERSE : Int32(0)) |
+                         (shared_matrices ? SOCP_F_SHARED_MATRICES : Int32(0)), h))
         ss = new(h[], Int32[0])
         finalizer(ss) do x
             x.handle == C_NULL || ccall((:socp_dense_destroy, libsocp), Cint, (Ptr{Cvoid},), x.handle)
@@ -219,7 +225,7 @@ end
 mutable struct HipSqrSolver <: KKTSolver{HipScaling}
     handle::Ptr{Cvoid}
     status::Vector{Int32}
-    function HipSqrSolver(pr::Problem{C,n,m,k,sing}) where {C,n,m,k,sing}
+    function HipSqrSolver(pr::Problem{C,n,m,k,sing}; shared_matrices::Bool=false) where {C,n,m,k,sing}
         kind, offs, dim = cone_arrays(pr.cones)
         dims = Ref(SocpDims(1, n, m, k, length(pr.cones)))
         A = Matrix{Float64}(pr.A)
@@ -229,7 +235,8 @@ mutable struct HipSqrSolver <: KKTSolver{HipScaling}
         socp_check(ccall((:socp_sqr_create, libsocp), Cint,
                          (Ptr{Cvoid}, Ref{SocpDims}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32},
                           Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Int32, Ptr{Ptr{Cvoid}}),
-                         socp_ctx(), dims, kind, offs, dim, A, G, singv, Int32(0), h))
+                         socp_ctx(), dims, kind, offs, dim, A, G, singv,
+                         shared_matrices ? SOCP_F_SHARED_MATRICES : Int32(0), h))
         ss = new(h[], Int32[0])
         finalizer(ss) do x
             x.handle == C_NULL || ccall((:socp_sqr_destroy, libsocp), Cint, (Ptr{Cvoid},), x.handle)
@@ -258,6 +265,17 @@ function solve_kkt(ss::HipSqrSolver, pr::Problem{C,n,m,k,sing}, s::State, scalin
 end
 
 # ------------------------------------------------------------ batched solve
+# shared_matrices=true: every problem's A, G and sing equal the first's; the
+# one problem whose matrices go to the device
+function check_shared(problems)
+    p0 = problems[1]
+    for (i, p) in enumerate(problems)
+        (p.A == p0.A && p.G == p0.G && typeof(p).parameters[5] == typeof(p0).parameters[5]) ||
+            throw(ArgumentError("shared_matrices=true: problem $i differs from problem 1 in A, G or sing"))
+    end
+    return problems[1:1]
+end
+
 """
     solve_socp_batched(problems; maxit=40, tol=1e-5, explicit_inverse=false) -> (states, iters, status)
 
@@ -267,24 +285,29 @@ problem in `status` (0 converged, 1 maxit, 2/3 PosDef, 4 domain) instead of
 throwing, so one bad problem does not abort the batch.  With
 `detect_infeasible=true` a problem without a solution stops with status 5
 (primal infeasible: `y, z` are the certificate) or 6 (dual infeasible: `x, s`
-are the ray) instead of running to `maxit`.
+are the ray) instead of running to `maxit`.  With `shared_matrices=true` (a
+parametric batch) every problem's `A`, `G` and `sing` must equal the first's
+(`ArgumentError` otherwise) and one copy of them goes to the device
+(`SOCP_F_SHARED_MATRICES`).
 """
 function solve_socp_batched(problems::AbstractVector{<:Problem}; maxit=40, tol=1e-5, explicit_inverse::Bool=false,
-                            detect_infeasible::Bool=false)
+                            detect_infeasible::Bool=false, shared_matrices::Bool=false)
     p0 = problems[1]
     n, m, k = p0.n, p0.m, p0.k
     B = length(problems)
     kind, offs, dim = cone_arrays(p0.cones)
+    mats = shared_matrices ? check_shared(problems) : problems
     c = reduce(vcat, [p.c for p in problems])
-    A = reduce(vcat, [vec(Matrix(p.A)) for p in problems])     # column-major per problem
+    A = reduce(vcat, [vec(Matrix(p.A)) for p in mats])     # column-major per problem
     b = reduce(vcat, [p.b for p in problems])
-    G = reduce(vcat, [vec(Matrix(p.G)) for p in problems])
+    G = reduce(vcat, [vec(Matrix(p.G)) for p in mats])
     h = reduce(vcat, [p.h for p in problems])
-    sing = UInt8[typeof(p).parameters[5] ? 1 : 0 for p in problems]
+    sing = UInt8[typeof(p).parameters[5] ? 1 : 0 for p in mats]
     x, y, z, s = zeros(B * n), zeros(B * m), zeros(B * k), zeros(B * k)
     iters, status = zeros(Int32, B), zeros(Int32, B)
     flags = (explicit_inverse ? SOCP_F_EXPLICIT_INVERSE : Int32(0)) |
-            (detect_infeasible ? SOCP_F_DETECT_INFEASIBLE : Int32(0))
+            (detect_infeasible ? SOCP_F_DETECT_INFEASIBLE : Int32(0)) |
+            (shared_matrices ? SOCP_F_SHARED_MATRICES : Int32(0))
     params = Ref(SocpParams(maxit, 3, tol, 0.99, 1e-10, flags, 0))
     dims = Ref(SocpDims(B, n, m, k, length(p0.cones)))
     rc = ccall((:socp_batch_solve, libsocp), Cint,
@@ -309,23 +332,25 @@ tested configuration, as one device solve (`socp_sqr_create` +
 `socp_sqr_solve_socp`; failures per problem, no throw).
 """
 function solve_socp_batched_sqr(problems::AbstractVector{<:Problem}; maxit=40, tol=1e-5,
-                                detect_infeasible::Bool=false)
+                                detect_infeasible::Bool=false, shared_matrices::Bool=false)
     p0 = problems[1]
     n, m, k = p0.n, p0.m, p0.k
     B = length(problems)
     kind, offs, dim = cone_arrays(p0.cones)
+    mats = shared_matrices ? check_shared(problems) : problems
     c = reduce(vcat, [p.c for p in problems])
-    A = reduce(vcat, [vec(Matrix(p.A)) for p in problems])
+    A = reduce(vcat, [vec(Matrix(p.A)) for p in mats])
     b = reduce(vcat, [p.b for p in problems])
-    G = reduce(vcat, [vec(Matrix(p.G)) for p in problems])
+    G = reduce(vcat, [vec(Matrix(p.G)) for p in mats])
     h = reduce(vcat, [p.h for p in problems])
-    sing = UInt8[typeof(p).parameters[5] ? 1 : 0 for p in problems]
+    sing = UInt8[typeof(p).parameters[5] ? 1 : 0 for p in mats]
     dims = Ref(SocpDims(B, n, m, k, length(p0.cones)))
     hd = Ref{Ptr{Cvoid}}(C_NULL)
     socp_check(ccall((:socp_sqr_create, libsocp), Cint,
                      (Ptr{Cvoid}, Ref{SocpDims}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32},
                       Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Int32, Ptr{Ptr{Cvoid}}),
-                     socp_ctx(), dims, kind, offs, dim, A, G, sing, Int32(0), hd))
+                     socp_ctx(), dims, kind, offs, dim, A, G, sing,
+                     shared_matrices ? SOCP_F_SHARED_MATRICES : Int32(0), hd))
     x, y, z, s = zeros(B * n), zeros(B * m), zeros(B * k), zeros(B * k)
     iters, status = zeros(Int32, B), zeros(Int32, B)
     params = Ref(SocpParams(maxit, 3, tol, 0.99, 1e-10, detect_infeasible ? SOCP_F_DETECT_INFEASIBLE : Int32(0), 0))

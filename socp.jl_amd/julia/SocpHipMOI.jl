@@ -89,7 +89,9 @@ end
 
 _opt(o::Optimizer, key, default) = get(Dict(o.options), key, default)
 
-function optimize_batched!(opts::AbstractVector{HipOptimizer})
+# shared_matrices=true: within every group the models' A and G must be equal
+# (ArgumentError otherwise); one copy goes to the device (SOCP_F_SHARED_MATRICES)
+function optimize_batched!(opts::AbstractVector{HipOptimizer}; shared_matrices::Bool=false)
     todo = [o for o in opts if o.inner.data !== nothing]
     groups = Dict{Any, Vector{HipOptimizer}}()
     for o in todo
@@ -99,7 +101,8 @@ function optimize_batched!(opts::AbstractVector{HipOptimizer})
     end
     for (key, group) in groups
         probs = [_hip_problem(o.inner) for o in group]
-        states, iters, status = solve_socp_batched(probs; maxit=key[5], tol=key[6], detect_infeasible=true)
+        states, iters, status = solve_socp_batched(probs; maxit=key[5], tol=key[6], detect_infeasible=true,
+                                                   shared_matrices=shared_matrices)
         for (o, st, it, ss) in zip(group, states, iters, status)
             o.inner.sol = st
             o.iters = it

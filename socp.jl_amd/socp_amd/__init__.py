@@ -21,7 +21,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import (CHOL_H_FAILED, CHOL_S_FAILED, CONE_POC, CONE_SOC, CONVERGED, DOMAIN_ERROR, DUAL_INFEASIBLE,
-                   F_DETECT_INFEASIBLE, F_DEVICE_PTRS, F_EXPLICIT_INVERSE, F_FORCE_LARGE, F_WARM_START, MAXIT,
+                   F_DETECT_INFEASIBLE, F_DEVICE_PTRS, F_EXPLICIT_INVERSE, F_FORCE_LARGE, F_SHARED_MATRICES,
+                   F_WARM_START, MAXIT,
                    PRIMAL_INFEASIBLE, Context, SocpError,
                    default_context,
                    default_params)
@@ -136,7 +137,7 @@ def _check_sizes(B, **arrays):
 
 def batch_solve(cones, n, m, k, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5, step=0.99,
                 sigma_exp=3, init_eps=1e-10, warm=None, ctx=None, res=False, out=None, force_large=False,
-                explicit_inverse=False, detect_infeasible=False):
+                explicit_inverse=False, detect_infeasible=False, shared_matrices=False):
     """Solve a batch of independent problems (same dims and cone structure).
 
     Arrays follow include/socp.h: per-problem column-major A (m x n), G (k x n)
@@ -153,6 +154,10 @@ def batch_solve(cones, n, m, k, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5,
     certificate's residual is below the context's tolerance
     (Context.set_infeasibility_tol, 1e-7) instead of running to maxit; not
     together with explicit_inverse.
+    shared_matrices (SOCP_F_SHARED_MATRICES): a parametric batch -- A is ONE
+    m x n matrix, G ONE k x n matrix and sing ONE byte (or None), used by every
+    problem; c, b, h stay per problem.  The outputs are bitwise those of the
+    same call on A, G and sing replicated B times.
     Returns dict(x, y, z, s, iters, status[, res]).
     """
     L = _lib.load()
@@ -160,8 +165,9 @@ def batch_solve(cones, n, m, k, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5,
     B = _size(c) // n
     if B * n != _size(c):
         raise ValueError(f"c: {_size(c)} elements is not a multiple of n={n}")
-    _check_sizes(B, A=(A if m else None, B * m * n), b=(b if m else None, B * m), G=(G, B * k * n),
-                 h=(h, B * k), sing=(sing, B))
+    MB = 1 if shared_matrices else B
+    _check_sizes(B, A=(A if m else None, MB * m * n), b=(b if m else None, B * m), G=(G, MB * k * n),
+                 h=(h, B * k), sing=(sing, MB))
     if warm is not None:
         wx, wy, wz, ws = warm
         _check_sizes(B, warm_x=(wx, B * n), warm_y=(wy if m else None, B * m), warm_z=(wz, B * k),
@@ -178,6 +184,8 @@ def batch_solve(cones, n, m, k, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5,
         flags |= F_EXPLICIT_INVERSE
     if detect_infeasible:
         flags |= F_DETECT_INFEASIBLE
+    if shared_matrices:
+        flags |= F_SHARED_MATRICES
     P = default_params(maxit=maxit, tol=tol, step=step, sigma_exp=sigma_exp, init_eps=init_eps,
                        flags=flags)
     if dev:
@@ -223,15 +231,17 @@ def batch_solve(cones, n, m, k, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5,
 
 
 def batch_kkt_solve(cones, n, m, k, A, G, sing, s, z, dx, dy, dz, ds, *, ctx=None, force_large=False,
-                    explicit_inverse=False):
+                    explicit_inverse=False, shared_matrices=False):
     """One KKT solve per problem at iterate (s, z): scaling + setup_iter + solve_kkt
-    (densesolver.jl:41-90) on the GPU.  Host (numpy) arrays.  Returns dict(cx,cy,cz,cs,status)."""
+    (densesolver.jl:41-90) on the GPU.  Host (numpy) arrays.  shared_matrices: A, G
+    and sing are the batch's one (as in ``batch_solve``).  Returns dict(cx,cy,cz,cs,status)."""
     L = _lib.load()
     kind, offs, dim = cone_arrays(cones)
     B = np.size(s) // k
     if B * k != np.size(s):
         raise ValueError(f"s: {np.size(s)} elements is not a multiple of k={k}")
-    _check_sizes(B, A=(A if m else None, B * m * n), G=(G, B * k * n), sing=(sing, B), z=(z, B * k),
+    MB = 1 if shared_matrices else B
+    _check_sizes(B, A=(A if m else None, MB * m * n), G=(G, MB * k * n), sing=(sing, MB), z=(z, B * k),
                  dx=(dx, B * n), dy=(dy if m else None, B * m), dz=(dz, B * k), ds=(ds, B * k))
     dims = _lib.Dims(B, n, m, k, len(kind))
     ctx = ctx or default_context()
@@ -244,7 +254,8 @@ def batch_kkt_solve(cones, n, m, k, A, G, sing, s, z, dx, dy, dz, ds, *, ctx=Non
                                 p(_host(dx)), p(_host(dy) if m else None), p(_host(dz)), p(_host(ds)),
                                 p(cx), p(cy if m else None), p(cz), p(cs), p(st),
                                 (F_FORCE_LARGE if force_large else 0)
-                                | (F_EXPLICIT_INVERSE if explicit_inverse else 0))
+                                | (F_EXPLICIT_INVERSE if explicit_inverse else 0)
+                                | (F_SHARED_MATRICES if shared_matrices else 0))
     _lib.check(rc)
     return dict(cx=cx, cy=cy[:B * m], cz=cz, cs=cs, status=st)
 
@@ -260,25 +271,42 @@ class DenseHandle:
     problem for setup_iter, n+m+2k for solve_kkt; ``h2d_bytes`` reports the last
     call's count).  torch CUDA inputs (A, G given as tensors): every later
     argument must be a device tensor too; calls are stream-ordered on torch's
-    current stream.  Results are bitwise those of ``batch_kkt_solve``."""
+    current stream.  Results are bitwise those of ``batch_kkt_solve``.
+
+    shared_matrices=True (SOCP_F_SHARED_MATRICES): A, G and sing are ONE m x n
+    matrix, ONE k x n matrix and ONE byte for all ``batch`` problems (``batch``
+    must then be given: G no longer tells it); the handle keeps that one copy,
+    the factor records stay per problem, and every result is bitwise that of
+    the handle built on the replicated matrices."""
 
     _pfx = "socp_dense"
 
     def _fn(self, name):
         return getattr(_lib.load(), f"{self._pfx}_{name}")
 
-    def __init__(self, cones, n, m, k, A, G, sing=None, *, ctx=None, force_large=False, explicit_inverse=False):
+    def __init__(self, cones, n, m, k, A, G, sing=None, *, ctx=None, force_large=False, explicit_inverse=False,
+                 shared_matrices=False, batch=None):
         self.cones, self.n, self.m, self.k = cones, n, m, k
         self.kind, self.offs, self.dim = cone_arrays(cones)
-        B = _size(G) // (k * n)
-        if B * k * n != _size(G):
-            raise ValueError(f"G: {_size(G)} elements is not a multiple of k*n={k * n}")
-        _check_sizes(B, A=(A if m else None, B * m * n), sing=(sing, B))
+        if shared_matrices:
+            if batch is None:
+                raise ValueError("shared_matrices=True needs batch= (the number of problems)")
+            B = int(batch)
+            _check_sizes(B, A=(A if m else None, m * n), G=(G, k * n), sing=(sing, 1))
+        else:
+            B = _size(G) // (k * n)
+            if B * k * n != _size(G):
+                raise ValueError(f"G: {_size(G)} elements is not a multiple of k*n={k * n}")
+            if batch is not None and int(batch) != B:
+                raise ValueError(f"batch={batch}, but G holds {B} problems")
+            _check_sizes(B, A=(A if m else None, B * m * n), sing=(sing, B))
         self.B = B
+        self.shared_matrices = bool(shared_matrices)
         self.ctx = ctx or default_context()
         self.dev = _is_torch(G)
         flags = ((F_DEVICE_PTRS if self.dev else 0) | (F_FORCE_LARGE if force_large else 0)
-                 | (F_EXPLICIT_INVERSE if explicit_inverse else 0))
+                 | (F_EXPLICIT_INVERSE if explicit_inverse else 0)
+                 | (F_SHARED_MATRICES if shared_matrices else 0))
         if self.dev:
             self.ctx.bind_torch_stream()
             arrs = (A if m else None, G, sing)
@@ -376,8 +404,8 @@ class SqrHandle(DenseHandle):
 
     _pfx = "socp_sqr"
 
-    def __init__(self, cones, n, m, k, A, G, sing=None, *, ctx=None):
-        super().__init__(cones, n, m, k, A, G, sing, ctx=ctx)
+    def __init__(self, cones, n, m, k, A, G, sing=None, *, ctx=None, shared_matrices=False, batch=None):
+        super().__init__(cones, n, m, k, A, G, sing, ctx=ctx, shared_matrices=shared_matrices, batch=batch)
 
     def factor(self, problem: int):
         """The factor L of H after modify_factors! for one problem (n x n lower
@@ -460,9 +488,15 @@ class Ingest:
     batch i's solve.  ``submit`` / ``submit_csc`` return a ticket, ``wait``
     returns the batch_solve dict; at most two tickets are outstanding.
     ``next_inputs()`` gives numpy views of the next slot's pinned input arrays
-    (a producer filling them in place saves the host copy)."""
+    (a producer filling them in place saves the host copy).
 
-    def __init__(self, cones, n, m, k, max_batch, *, ctx=None, force_large=False):
+    shared_matrices=True (SOCP_F_SHARED_MATRICES): the slots stage no A, G or
+    sing; ``set_matrices(A, G, sing=None)`` gives the one A, G and sing byte of
+    every later batch (only with no ticket outstanding; again between batches
+    as needed), ``submit(c, None, b, None, h)`` carries the vectors alone and
+    ``next_inputs()`` has no A, G, sing."""
+
+    def __init__(self, cones, n, m, k, max_batch, *, ctx=None, force_large=False, shared_matrices=False):
         L = _lib.load()
         self.cones, self.n, self.m, self.k, self.max_batch = cones, n, m, k, int(max_batch)
         self.kind, self.offs, self.dim = cone_arrays(cones)
@@ -471,9 +505,22 @@ class Ingest:
         dims = _lib.Dims(self.max_batch, n, m, k, len(self.kind))
         p = _lib.ptr
         _lib.check(L.socp_ingest_create(self.ctx.handle, dims, p(self.kind), p(self.offs), p(self.dim),
-                                        F_FORCE_LARGE if force_large else 0, C.byref(h)))
+                                        (F_FORCE_LARGE if force_large else 0)
+                                        | (F_SHARED_MATRICES if shared_matrices else 0), C.byref(h)))
         self.handle = h
+        self.shared_matrices = bool(shared_matrices)
         self._batch = {}
+
+    def set_matrices(self, A, G, sing=None):
+        """The one A (m x n), G (k x n), column-major, and sing byte (None: the
+        device probe) of every later batch of a shared ingest
+        (socp_ingest_set_matrices): host arrays, copied synchronously."""
+        n, m, k = self.n, self.m, self.k
+        _check_sizes(1, A=(A if m else None, m * n), G=(G, k * n), sing=(sing, 1))
+        p = _lib.ptr
+        _lib.check(_lib.load().socp_ingest_set_matrices(
+            self.handle, p(_host(A) if m else None), p(_host(G)),
+            p(None if sing is None else _host(sing, np.uint8))))
 
     def close(self):
         if getattr(self, "handle", None):
@@ -494,6 +541,8 @@ class Ingest:
         for key, q, cnt, ct in zip(("c", "A", "b", "G", "h", "sing"), ptrs,
                                    (B * n, B * m * n, B * m, B * k * n, B * k, B),
                                    (C.c_double,) * 5 + (C.c_uint8,)):
+            if self.shared_matrices and key in ("A", "G", "sing"):
+                continue  # NULL: a shared ingest stages none of them
             out[key] = np.ctypeslib.as_array(C.cast(q, C.POINTER(ct)), shape=(max(cnt, 1),))[:cnt]
         return out
 
@@ -510,7 +559,7 @@ class Ingest:
         t = C.c_int64()
         P = self._params(maxit, tol, step, sigma_exp, init_eps, detect_infeasible)
         p = _lib.ptr
-        arr = [_host(c), _host(A) if m else None, _host(b) if m else None, _host(G), _host(h),
+        arr = [_host(c), _host(A) if m and A is not None else None, _host(b) if m else None, _host(G), _host(h),
                None if sing is None else _host(sing, np.uint8)]
         _lib.check(_lib.load().socp_ingest_submit(self.handle, B, *[p(a) for a in arr], P, C.byref(t)))
         self._batch[t.value] = B
@@ -793,29 +842,41 @@ def solve_socp(prob: Problem, ss: SolverState) -> State:
     return State(prob, out["x"], out["y"], out["z"], out["s"])
 
 
-def solve_socp_batched(problems, maxit=40, tol=1e-5, ctx=None, solver="dense", detect_infeasible=False):
+def solve_socp_batched(problems, maxit=40, tol=1e-5, ctx=None, solver="dense", detect_infeasible=False,
+                       shared_matrices=False):
     """Batched solve of Problems sharing dims and cones; returns (states, iters, status)
     without raising: failures are reported per problem.  solver="dense": the
     DenseSolver path (the fused register / blocked kernels); "sqr": the
     SparseSolver rank-update path (SqrHandle.solve_socp).  detect_infeasible as
     in ``batch_solve``: statuses PRIMAL_INFEASIBLE / DUAL_INFEASIBLE with the
-    certificate in the returned state."""
+    certificate in the returned state.  shared_matrices=True: a parametric
+    batch -- every problem's A, G and sing must equal the first's (ValueError
+    otherwise); one copy of them goes to the device (SOCP_F_SHARED_MATRICES)."""
     p0 = problems[0]
     n, m, k = p0.n, p0.m, p0.k
     for p in problems:
         assert (p.n, p.m, p.k) == (n, m, k)
+    if shared_matrices:
+        for i, p in enumerate(problems):
+            for name in ("A", "G"):
+                if not np.array_equal(getattr(p, name), getattr(p0, name)):
+                    raise ValueError(f"shared_matrices=True: problem {i}'s {name} differs from problem 0's")
+            if bool(p.sing) != bool(p0.sing):
+                raise ValueError(f"shared_matrices=True: problem {i}'s sing differs from problem 0's")
+    mats = [p0] if shared_matrices else problems
     c = np.concatenate([p.c for p in problems])
-    A = np.concatenate([_colmajor(p.A, m, n) for p in problems]) if m else None
+    A = np.concatenate([_colmajor(p.A, m, n) for p in mats]) if m else None
     b = np.concatenate([p.b for p in problems]) if m else None
-    G = np.concatenate([_colmajor(p.G, k, n) for p in problems])
+    G = np.concatenate([_colmajor(p.G, k, n) for p in mats])
     h = np.concatenate([p.h for p in problems])
-    sing = np.array([p.sing for p in problems], np.uint8)
+    sing = np.array([p.sing for p in mats], np.uint8)
     if solver == "sqr":
-        out = SqrHandle(p0.cones, n, m, k, A, G, sing, ctx=ctx).solve_socp(
+        out = SqrHandle(p0.cones, n, m, k, A, G, sing, ctx=ctx, shared_matrices=shared_matrices,
+                        batch=len(problems)).solve_socp(
             c, b, h, maxit=maxit, tol=tol, detect_infeasible=detect_infeasible)
     else:
         out = batch_solve(p0.cones, n, m, k, c, A, b, G, h, sing, maxit=maxit, tol=tol, ctx=ctx,
-                          detect_infeasible=detect_infeasible)
+                          detect_infeasible=detect_infeasible, shared_matrices=shared_matrices)
     states = [State(p, out["x"][i * n:(i + 1) * n], out["y"][i * m:(i + 1) * m],
                     out["z"][i * k:(i + 1) * k], out["s"][i * k:(i + 1) * k])
               for i, p in enumerate(problems)]

@@ -21,6 +21,7 @@ PRIMAL_INFEASIBLE, DUAL_INFEASIBLE = 5, 6  # with F_DETECT_INFEASIBLE only
 CONE_POC, CONE_SOC = 0, 1
 F_DEVICE_PTRS, F_WARM_START, F_FORCE_LARGE, F_EXPLICIT_INVERSE = 1, 2, 4, 8
 F_DETECT_INFEASIBLE = 256  # bits 16..128 are the CPU oracle's
+F_SHARED_MATRICES = 512  # one A, G, sing for the whole batch (SOCP_F_SHARED_MATRICES)
 
 EXPORTED = [
     "socp_last_error", "socp_version", "socp_params_default", "socp_ctx_create",
@@ -31,7 +32,7 @@ EXPORTED = [
     "socp_comm_destroy", "socp_allgather_status", "socp_allgather_outcomes",
     "socp_dense_create", "socp_dense_setup_iter", "socp_dense_solve_kkt", "socp_dense_h2d_bytes",
     "socp_dense_record_bytes", "socp_dense_destroy",
-    "socp_ingest_create", "socp_ingest_next_inputs", "socp_ingest_submit", "socp_ingest_submit_csc",
+    "socp_ingest_create", "socp_ingest_set_matrices", "socp_ingest_next_inputs", "socp_ingest_submit", "socp_ingest_submit_csc",
     "socp_ingest_wait", "socp_ingest_destroy",
     "socp_sqr_supported", "socp_sqr_create", "socp_sqr_setup_iter", "socp_sqr_solve_kkt", "socp_sqr_factor",
     "socp_sqr_scaling", "socp_sqr_h2d_bytes", "socp_sqr_record_bytes", "socp_sqr_destroy",
@@ -138,6 +139,8 @@ def load():
     if hasattr(L, "socp_ingest_create"):  # pipelined ingest (absent from older A/B builds)
         L.socp_ingest_create.argtypes = common + [C.c_int32, C.POINTER(C.c_void_p)]
         L.socp_ingest_next_inputs.argtypes = [vp] + [C.POINTER(C.c_void_p)] * 6
+        if hasattr(L, "socp_ingest_set_matrices"):  # shared matrices (absent from older A/B builds)
+            L.socp_ingest_set_matrices.argtypes = [vp, dp, dp, u8p]
         L.socp_ingest_submit.argtypes = [vp, C.c_int64] + [dp] * 5 + [u8p, C.POINTER(Params), C.POINTER(C.c_int64)]
         L.socp_ingest_submit_csc.argtypes = ([vp, C.c_int64] + [dp] * 3 + [u8p] + [vp] * 4 + [vp] * 4
                                              + [C.c_int32, C.POINTER(Params), C.POINTER(C.c_int64)])

@@ -292,11 +292,14 @@ class Optimizer:
         return (sol.y if ci.set_type is Zeros else sol.z)[rows].copy()
 
 
-def optimize_batched(optimizers, ctx=None):
+def optimize_batched(optimizers, ctx=None, shared_matrices=False):
     """`MOI.optimize!` for many models at once: models are grouped by structure
     (n, equality rows, Nonnegatives length, SOC dimensions) and each group is one
     `socp_batch_solve` launch, with infeasibility detection on
-    (SOCP_F_DETECT_INFEASIBLE).  Per-model options `maxit`/`tol` must agree within a group."""
+    (SOCP_F_DETECT_INFEASIBLE).  Per-model options `maxit`/`tol` must agree within a group.
+    shared_matrices=True: a parametric batch -- within every group each model's A
+    and G (and with them `sing`) must equal the group's first (ValueError
+    otherwise), and one copy of them goes to the device (SOCP_F_SHARED_MATRICES)."""
     groups: "OrderedDict[tuple, list]" = OrderedDict()
     for o in optimizers:
         d = o.build()
@@ -307,13 +310,19 @@ def optimize_batched(optimizers, ctx=None):
         maxit, tol = key[4], key[5]
         k = l + sum(qa)
         ds = [o.data for o in opts]
-        sing = np.array([_sing(d.G) for d in ds], np.uint8)
+        if shared_matrices:
+            for i, d in enumerate(ds):
+                if (f and not np.array_equal(d.A, ds[0].A)) or not np.array_equal(d.G, ds[0].G):
+                    raise ValueError(f"shared_matrices=True: model {i} of its group differs from the first in A or G")
+        ms = ds[:1] if shared_matrices else ds
+        sing = np.array([_sing(d.G) for d in ms], np.uint8)
         c = np.concatenate([d.c for d in ds])
-        A = np.concatenate([d.A.ravel(order="F") for d in ds]) if f else None
+        A = np.concatenate([d.A.ravel(order="F") for d in ms]) if f else None
         b = np.concatenate([d.b for d in ds]) if f else None
-        G = np.concatenate([d.G.ravel(order="F") for d in ds])
+        G = np.concatenate([d.G.ravel(order="F") for d in ms])
         h = np.concatenate([d.h for d in ds])
         out = batch_solve(ds[0].cones, n, f, k, c, A, b, G, h, sing, maxit=maxit, tol=tol, detect_infeasible=True,
+                          shared_matrices=shared_matrices,
                           ctx=ctx if ctx is not None else opts[0].options.get("ctx"))
         for i, o in enumerate(opts):
             o._set_solution(out["x"][i * n:(i + 1) * n], out["y"][i * f:(i + 1) * f],
