@@ -444,9 +444,17 @@ __device__ __forceinline__ double dpp(double v) {
   const int h2 = __builtin_amdgcn_update_dpp(0, hi, CTRL, RM, 0xF, false);
   return __hiloint2double(h2, l2);
 }
+#ifndef SOCP_DPP_B64
+#define SOCP_DPP_B64 1  // 0: row_newbcast of a double as two 32-bit moves too (A/B builds)
+#endif
 // DPP move whose pattern writes every lane (row_newbcast): no old value needed.
+// row_newbcast:N (0x150 + N) of a double is one v_mov_b64_dpp; every other
+// control has no 64-bit form and moves the two halves.
 template <int CTRL>
 __device__ __forceinline__ double dpp_all(double v) {
+#if SOCP_DPP_B64
+  if constexpr (CTRL >= 0x150 && CTRL <= 0x15F) return __builtin_amdgcn_mov_dpp(v, CTRL, 0xF, 0xF, false);
+#endif
   const int l2 = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, false);
   const int h2 = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, false);
   return __hiloint2double(h2, l2);
@@ -760,7 +768,7 @@ __device__ __forceinline__ double rsqrt_tile(double d) {
 }
 
 #ifndef SOCP_TILE_FACTOR
-#define SOCP_TILE_FACTOR 1
+#define SOCP_TILE_FACTOR 2  // 2: pivot blocks in lanes; 1: in wave-uniform values; 0: per pivot (A/B builds)
 #endif
 #ifndef SOCP_TRANSPOSE_MFMA
 #define SOCP_TRANSPOSE_MFMA 0
@@ -806,14 +814,16 @@ __device__ __forceinline__ void tile_pivot(double& v, double& w, double& R, doub
 #endif
 // Row blocks B.. of W = L^-1 for D = L L' (right-looking, 4 rows at a time;
 // the rank-4 trailing update of the D and identity tiles is one MFMA each).
-// The 4x4 diagonal block is factored in wave-uniform values (its upper
-// triangle, as potrf('U') reads it), then every lane forms the block's rows
-// of R = L' and of W by forward substitution from the broadcast block rows.
+// Every lane forms the block's rows of R = L' and of W by forward
+// substitution from the broadcast block rows; the 4x4 diagonal block (its
+// upper triangle, as potrf('U') reads it) is read out of those rows by in-row
+// broadcasts (SOCP_TILE_FACTOR 1: factored beforehand in wave-uniform values,
+// the same operations on the same values).
 struct NoHook {
   template <int B>
   __device__ __forceinline__ void run() const {}
 };
-template <int B, bool INPL = (SOCP_TILE_INPLACE != 0), class H = NoHook>
+template <int B, bool INPL = (SOCP_TILE_INPLACE != 0), bool LANES = (SOCP_TILE_FACTOR == 2), class H = NoHook>
 __device__ __forceinline__ void tile_block(d4& Dt, d4& It, d4& W, bool& ok, const H& hook = H()) {
   if constexpr (B < 4) {
     LANE_IDS();
@@ -826,7 +836,39 @@ __device__ __forceinline__ void tile_block(d4& Dt, d4& It, d4& W, bool& ok, cons
       tile_pivot<B, 0>(v, w, R, Wb, ok);
     }
 #else
-    {
+    if constexpr (LANES) {
+      // V[i], X[i]: rows 4B+i of the D and identity tiles in every row group.
+      // Row R_i of L' holds the pivot block's own entries at columns 4B..4B+3
+      // (r_ij = R_i at column 4B+j, the pivot d_i = T_i at column 4B+i), so
+      // they are in-row broadcasts of values the lanes form anyway
+      double V[4], X[4];
+      row_bcast4(Dt[B], V);
+      row_bcast4(It[B], X);
+      const double rs0 = rsqrt_tile(dpp_all<0x150 + 4 * B>(V[0]));
+      const double R0 = V[0] * rs0, W0 = X[0] * rs0;
+      const double r01 = dpp_all<0x150 + 4 * B + 1>(R0), r02 = dpp_all<0x150 + 4 * B + 2>(R0),
+                   r03 = dpp_all<0x150 + 4 * B + 3>(R0);
+      const double T1 = fma(-r01, R0, V[1]), Y1 = fma(-r01, W0, X[1]);
+      const double rs1 = rsqrt_tile(dpp_all<0x150 + 4 * B + 1>(T1));
+      const double R1 = T1 * rs1, W1 = Y1 * rs1;
+      const double r12 = dpp_all<0x150 + 4 * B + 2>(R1), r13 = dpp_all<0x150 + 4 * B + 3>(R1);
+      const double T2 = fma(-r12, R1, fma(-r02, R0, V[2])), Y2 = fma(-r12, W1, fma(-r02, W0, X[2]));
+      const double rs2 = rsqrt_tile(dpp_all<0x150 + 4 * B + 2>(T2));
+      const double R2 = T2 * rs2, W2 = Y2 * rs2;
+      const double r23 = dpp_all<0x150 + 4 * B + 3>(R2);
+      const double T3 = fma(-r23, R2, fma(-r13, R1, fma(-r03, R0, V[3]))),
+                   Y3 = fma(-r23, W2, fma(-r13, W1, fma(-r03, W0, X[3])));
+      const double rs3 = rsqrt_tile(dpp_all<0x150 + 4 * B + 3>(T3));
+      const double R3 = T3 * rs3, W3 = Y3 * rs3;
+#if !SOCP_TILE_OKDIAG
+      {
+        const double dv = g == 0 ? V[0] : (g == 1 ? T1 : (g == 2 ? T2 : T3));
+        ok = ok && __all(cl != 4 * B + g || dv > 0.0);  // NaN fails too
+      }
+#endif
+      R = g == 0 ? R0 : (g == 1 ? R1 : (g == 2 ? R2 : R3));
+      Wb = g == 0 ? W0 : (g == 1 ? W1 : (g == 2 ? W2 : W3));
+    } else {
       const double v = Dt[B], w = It[B];
       // a_ij = D[4B+i][4B+j] (i <= j): lane (i, 4B+j) of register B
       const double a00 = readlane_d(v, 4 * B), a01 = readlane_d(v, 4 * B + 1),
@@ -879,14 +921,16 @@ __device__ __forceinline__ void tile_block(d4& Dt, d4& It, d4& W, bool& ok, cons
         It[r] = u[r];
       }
     }
-    tile_block<B + 1, INPL>(Dt, It, W, ok, hook);
+    tile_block<B + 1, INPL, LANES>(Dt, It, W, ok, hook);
   }
 }
 // INPL: the trailing updates replace the tiles whole (one factorisation 3,126
 // cycles vs 3,406 on one wave, profiles/r03_probe_tile.log); the copying form
 // keeps fewer registers live, which the smallest register kernels need to stay
 // at two waves per SIMD.
-template <bool INPL = (SOCP_TILE_INPLACE != 0), class H = NoHook>
+// LANES: the pivot blocks in lanes (SOCP_TILE_FACTOR 2) or in wave-uniform
+// values; the same operations on the same values, so the same bits.
+template <bool INPL = (SOCP_TILE_INPLACE != 0), bool LANES = (SOCP_TILE_FACTOR == 2), class H = NoHook>
 __device__ __forceinline__ void factor_tile(d4 Dt, d4& W, bool& ok, const H& hook = H()) {
   MARK_BEGIN("factor_tile");
   LANE_IDS();
@@ -894,7 +938,7 @@ __device__ __forceinline__ void factor_tile(d4 Dt, d4& W, bool& ok, const H& hoo
 #pragma unroll
   for (int r = 0; r < 4; ++r) It[r] = (g + 4 * r == cl) ? 1.0 : 0.0;
   W = It;
-  tile_block<0, INPL>(Dt, It, W, ok, hook);
+  tile_block<0, INPL, LANES>(Dt, It, W, ok, hook);
 #if SOCP_TILE_OKDIAG
   // potrf's test once per tile: the diagonal of W = L^-1 holds the pivots'
   // 1/sqrt, which is finite and > 0 exactly when every pivot is > 0 (a pivot
@@ -933,6 +977,11 @@ struct Small {
   // waves per SIMD: C1's <2, 12, 1> takes 209 + 48 registers with them, 208 + 48
   // without
   static constexpr bool TILE_INPL = SOCP_TILE_INPLACE != 0 && NQ * NP > 24;
+  // the tile's pivot blocks in lanes (SOCP_TILE_FACTOR 2) on the m <= 16
+  // shapes.  The m > 16 shapes keep the wave-uniform form: with the lane form
+  // <2, 4, 2> takes 247 registers instead of 231 and falls to one wave per
+  // SIMD, and three more NQ = 4 objects trip the compiler's AGPR-rewrite pass
+  static constexpr bool TILE_LANES = SOCP_TILE_FACTOR == 2 && MQ == 1;
   // the solves' per-cone constants read ahead of the cone reductions (their
   // latency under the DPP chains) where registers allow: not in the kernels
   // that keep two waves per SIMD (C1's <2, 12, 1> would take 217 + 48; every
@@ -2506,10 +2555,10 @@ struct Small {
         M[tri(P + 1, P + 1)] = mm<1>(Y[P + 1], Y[P + 1], M[tri(P + 1, P + 1)]);
         d4 Wn;
 #if SOCP_SWEEP_LOOKAHEAD
-        factor_tile<TILE_INPL>(M[tri(P + 1, P + 1)], Wn, ok, PanelHook<Q, P>{M, Y, W});
+        factor_tile<TILE_INPL, TILE_LANES>(M[tri(P + 1, P + 1)], Wn, ok, PanelHook<Q, P>{M, Y, W});
 #else
         do_panel_ops<Q, P, 0, panel_op_count<Q, P>()>(M, Y, W);
-        factor_tile<TILE_INPL>(M[tri(P + 1, P + 1)], Wn, ok);
+        factor_tile<TILE_INPL, TILE_LANES>(M[tri(P + 1, P + 1)], Wn, ok);
 #endif
         STAMP_SUB(1);
         sweep_panel<Q, SUBST, P + 1>(M, Id, Wn, ok);
@@ -2522,7 +2571,7 @@ struct Small {
   template <int Q, bool SUBST>
   __device__ __forceinline__ void sweep_tiles(d4 (&M)[Q * (Q + 1) / 2], const d4& Id, bool& ok) {
     d4 W;
-    factor_tile<TILE_INPL>(M[tri(0, 0)], W, ok);
+    factor_tile<TILE_INPL, TILE_LANES>(M[tri(0, 0)], W, ok);
     STAMP_SUB(0);
     sweep_panel<Q, SUBST, 0>(M, Id, W, ok);
   }
@@ -2633,7 +2682,7 @@ struct Small {
         T[tri(P + 1, P)] = mm<0>(WT, T[tri(P + 1, P)], (d4){0.0, 0.0, 0.0, 0.0});
         T[tri(P + 1, P + 1)] = mm<1>(T[tri(P + 1, P)], T[tri(P + 1, P)], T[tri(P + 1, P + 1)]);
         d4 Wn;
-        factor_tile<TILE_INPL>(T[tri(P + 1, P + 1)], Wn, ok, CholHook<P>{*this, WT});
+        factor_tile<TILE_INPL, TILE_LANES>(T[tri(P + 1, P + 1)], Wn, ok, CholHook<P>{*this, WT});
         T[tri(P, P)] = W;
         chol_panel<P + 1>(Wn, ok);
       } else {
@@ -2652,7 +2701,7 @@ struct Small {
     Sv[0] = (d4){0.0, 0.0, 0.0, 0.0};
     bool ok = true;
     d4 W;
-    factor_tile<TILE_INPL>(T[tri(0, 0)], W, ok);
+    factor_tile<TILE_INPL, TILE_LANES>(T[tri(0, 0)], W, ok);
     chol_panel<0>(W, ok);
     SYNC();
     return ok;
@@ -2723,7 +2772,7 @@ struct Small {
         M[tri(P + 1, P)] = mm<0>(WT, M[tri(P + 1, P)], (d4){0.0, 0.0, 0.0, 0.0});
         M[tri(P + 1, P + 1)] = mm<1>(M[tri(P + 1, P)], M[tri(P + 1, P)], M[tri(P + 1, P + 1)]);
         d4 Wn;
-        factor_tile<TILE_INPL>(M[tri(P + 1, P + 1)], Wn, ok, GCholHook<Q, P>{M, WT});
+        factor_tile<TILE_INPL, TILE_LANES>(M[tri(P + 1, P + 1)], Wn, ok, GCholHook<Q, P>{M, WT});
         M[tri(P, P)] = W;
         gchol_panel<Q, P + 1>(M, Wn, ok);
       } else {
@@ -2738,7 +2787,7 @@ struct Small {
     bool ok = true;
     {
       d4 W;
-      factor_tile<TILE_INPL>(M[tri(0, 0)], W, ok);
+      factor_tile<TILE_INPL, TILE_LANES>(M[tri(0, 0)], W, ok);
       gchol_panel<Q, 0>(M, W, ok);
     }
     // Y = L^-1: row a reads rows q < a of Y (done) and row a of L from column b up
@@ -2836,7 +2885,7 @@ struct Small {
       bool okS = true;
       if (!(SOCP_KO & 8)) {
         d4 Ws;
-        factor_tile<TILE_INPL>(Sv[0], Ws, okS);
+        factor_tile<TILE_INPL, TILE_LANES>(Sv[0], Ws, okS);
         Sv[0] = mm<0>(Ws, Ws, (d4){0.0, 0.0, 0.0, 0.0});
       }
       clear_tb();

@@ -57,7 +57,8 @@ L0, h0 = libs[0][1], libs[0][2]
 assert L0.socp_generate(h0, C.byref(dims), kind, offs, dim, cfg.seed, 0, *map(P0, (c, A, b, G, h))) == 0
 L0.socp_ctx_sync(h0)
 sing = torch.zeros(B, dtype=torch.uint8, device=dev)
-params = _lib.default_params(maxit=K, tol=0.0, flags=_lib.F_DEVICE_PTRS)
+XI = _lib.F_EXPLICIT_INVERSE if os.environ.get("AB_XI") == "1" else 0  # AB_XI=1: SOCP_F_EXPLICIT_INVERSE
+params = _lib.default_params(maxit=K, tol=0.0, flags=_lib.F_DEVICE_PTRS | XI)
 outs = []
 for _ in libs:
     outs.append(dict(x=torch.empty(B * n, **f64), y=torch.empty(B * max(m, 1), **f64), z=torch.empty(B * k, **f64),
@@ -82,5 +83,9 @@ for i, (p, _, _) in enumerate(libs):
     x = outs[i]["x"].view(B, n)
     rel = ((x - x0).norm(dim=1) / x0.norm(dim=1).clamp_min(1e-300)).max().item()
     st = torch.bincount(outs[i]["st"].long(), minlength=5).tolist()
+    # every output against the first library's, bit for bit (NaNs of failed problems included)
+    diff = [key for key in ("x", "y", "z", "s", "it", "st")
+            if not (key == "y" and m == 0) and not torch.equal(outs[i][key].view(torch.uint8), outs[0][key].view(torch.uint8))]
     print(f"{sys.argv[1]} {os.path.relpath(p)}: median {t[len(t)//2]:.3f} ms  min {t[0]:.3f} ms  "
-          f"max rel dx vs first {rel:.2e}  status {st}  iters {int(outs[i]['it'].sum())}", flush=True)
+          f"max rel dx vs first {rel:.2e}  bitwise {'equal' if not diff else 'DIFFERS in ' + ','.join(diff)}  "
+          f"status {st}  iters {int(outs[i]['it'].sum())}", flush=True)
