@@ -214,6 +214,38 @@ int socp_batch_solve_ex(socp_ctx* ctx, const socp_dims* dims,
                         double* x, double* y, double* z, double* s,
                         int32_t* iters, int32_t* status, double* res);
 
+/* Quadratic objectives: minimise x'Px/2 + c'x subject to the same constraints.
+ * Arguments as for socp_batch_solve_ex (res may be NULL), plus
+ *   P : per problem n x n, column-major: P[p*n*n + j*n + i] = P_p(i,j).  It is
+ *       read in full and must be symmetric positive semidefinite.  Neither is
+ *       checked on the device: an unsymmetric P gives unspecified results, and
+ *       a P that makes H indefinite gives SOCP_CHOL_H_FAILED for that problem
+ *       only.  With SOCP_F_SHARED_MATRICES P is ONE n x n matrix, like A and G,
+ *       and the results are the bits of the replicated call.
+ * The method is that of socp_batch_solve_ex with two changes: the dual
+ * residual is rd = Px + A'y + G'z + c wherever it appears (the exit test, the
+ * right-hand sides, res[0]), and the reduced KKT matrix is
+ * H = P + G'W^-2 G (+A'A when sing); the initial point solves the W = I
+ * system with H0 = P + G'G (+A'A).  `sing` keeps its meaning (cholesky(G'G)
+ * fails), and the sing == NULL probe factors G'G alone.  The reference already
+ * takes one common step length for the primal and the dual (solver.jl:146-150),
+ * as a QP requires.
+ * P == NULL runs exactly what socp_batch_solve_ex runs (the same kernel, the
+ * same bits).  Flags honoured: SOCP_F_DEVICE_PTRS (stream-ordered),
+ * SOCP_F_WARM_START, SOCP_F_FORCE_LARGE, SOCP_F_SHARED_MATRICES.  With a P,
+ * SOCP_F_EXPLICIT_INVERSE and SOCP_F_DETECT_INFEASIBLE return
+ * SOCP_E_UNSUPPORTED (no QP kernel is compiled in the explicit-inverse order;
+ * the unboundedness rule would need Px = 0 as well); socp_last_error says so.
+ * The dims gate is socp_supported's.  The SOCP_DUMP_DIR dump also writes
+ * problem<p>_P.txt. */
+int socp_batch_solve_qp(socp_ctx* ctx, const socp_dims* dims,
+                        const int32_t* cone_kind, const int32_t* cone_offs, const int32_t* cone_dim,
+                        const double* P, const double* c, const double* A, const double* b,
+                        const double* G, const double* h, const uint8_t* sing,
+                        const socp_params* params,
+                        double* x, double* y, double* z, double* s,
+                        int32_t* iters, int32_t* status, double* res);
+
 /* Single-problem plugin entries.  They replace the two KKTSolver methods of
  * DenseSolver so the reference's own KKT golden (runtests.jl:95-128) runs
  * through the HIP path:

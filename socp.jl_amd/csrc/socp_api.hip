@@ -72,7 +72,7 @@ struct socp_ctx {
   const char* last_name = "";
   double itol = 1e-7;  // SOCP_F_DETECT_INFEASIBLE's tolerance (socp_ctx_set_infeasibility_tol)
   enum { B_C, B_A, B_B, B_G, B_H, B_SING, B_X, B_Y, B_Z, B_S, B_IT, B_ST, B_RES, B_DX, B_DY,
-         B_DZ, B_DS, B_CX, B_CY, B_CZ, B_CS, B_CNT, B_LWS, B_ERR, NB };
+         B_DZ, B_DS, B_CX, B_CY, B_CZ, B_CS, B_CNT, B_LWS, B_ERR, B_P, NB };
   DevBuf buf[NB];
 };
 
@@ -362,7 +362,8 @@ static bool fuse_u_enabled() {
   return !(e && e[0] == '0' && e[1] == '\0');
 }
 
-static int launch_small(socp_ctx* ctx, SmallArgs& args, const SmallVariant* v) {
+// qp: the QP solver (socp_batch_solve_qp; args carries P, small_set_qp)
+static int launch_small(socp_ctx* ctx, SmallArgs& args, const SmallVariant* v, bool qp = false) {
   args.al_rows = cone_rows_uniform(args.cones, args.nc);
   // (cones of 32 or 64 rows on a variant of whole 8-row-step chunks: a G x chunk lies in one cone)
   args.fuse_u = 0;
@@ -378,13 +379,14 @@ static int launch_small(socp_ctx* ctx, SmallArgs& args, const SmallVariant* v) {
   const bool xi = (args.flags & SOCP_F_EXPLICIT_INVERSE) != 0 && v->xi_kernel;
   // SOCP_F_DETECT_INFEASIBLE: the solver instantiation with the rule (never with xi: check_detect_flags)
   const bool di = solver && !xi && (args.flags & SOCP_F_DETECT_INFEASIBLE) != 0;
-  const void* kern = di   ? v->di_kernel
+  const void* kern = qp   ? v->qp_kernel
+                     : di ? v->di_kernel
                      : xi ? (solver ? v->xi_kernel : v->xi_kkt_kernel)
                           : (solver ? v->kernel : v->kkt_kernel);
   // the slot plan: the plain solver only -- the kernel compiled for the table's pair of pure slots
   // (the plugin entries keep their records' layout; the xi and di solvers keep their one kernel)
   args.slot_rot = args.slot_kinds = 0;
-  if (solver && !xi && !di) {
+  if (solver && !xi && !di && !qp) {  // (the QP solver is compiled for mixed slots only)
     int32_t rot = 0, kinds = 0;
     small_slot_plan(args.cones, args.nc, args.k, args.al_rows, slot_specialise_enabled(), rot, kinds);
     const int pair = slot_pair_of(kinds & 15, kinds >> 4);
@@ -409,17 +411,21 @@ static int launch_small(socp_ctx* ctx, SmallArgs& args, const SmallVariant* v) {
   HIPCHK(timing_begin(ctx));
   HIPCHK(hipLaunchKernel(kern, dim3((unsigned)blocks), dim3(64), kargs, lds, ctx->stream));
   HIPCHK(timing_end(ctx));
-  ctx->last_name = di ? v->di_name : xi ? (solver ? v->xi_name : v->xi_kkt_name) : (solver ? v->name : v->kkt_name);
+  ctx->last_name = qp   ? v->qp_name
+                   : di ? v->di_name
+                   : xi ? (solver ? v->xi_name : v->xi_kkt_name)
+                        : (solver ? v->name : v->kkt_name);
   return 0;
 }
 
-static int launch_large(socp_ctx* ctx, const SmallArgs& a, double* rec = nullptr) {
+static int launch_large(socp_ctx* ctx, const SmallArgs& a, double* rec = nullptr, bool qp = false) {
   size_t lds = 0;
   bool gv = false;
   const bool xi = (a.flags & SOCP_F_EXPLICIT_INVERSE) != 0;
   if (!large_fits(a.n, a.m, a.k, a.nc, &lds, &gv, xi)) return fail(SOCP_E_UNSUPPORTED, kUnsupported);
   const bool di = a.mode == MODE_SOLVE && !xi && (a.flags & SOCP_F_DETECT_INFEASIBLE) != 0;
-  const void* kern = large_kernel_ptr(xi, gv, di);
+  const void* kern = large_kernel_ptr(xi, gv, di, qp);
+  if (!kern) return fail(SOCP_E_UNSUPPORTED, "no compiled kernel for these flags");
   HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   int per_cu = 0;
   HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 512, lds));
@@ -441,7 +447,7 @@ static int launch_large(socp_ctx* ctx, const SmallArgs& a, double* rec = nullptr
   HIPCHK(timing_begin(ctx));
   HIPCHK(hipLaunchKernel(kern, dim3((unsigned)grid), dim3(512), kargs, lds, ctx->stream));
   HIPCHK(timing_end(ctx));
-  ctx->last_name = large_kernel_name(xi, gv, di);
+  ctx->last_name = large_kernel_name(xi, gv, di, qp);
   return 0;
 }
 
@@ -497,6 +503,7 @@ static int copy_back(socp_ctx* ctx, T* user, const T* devp, size_t count, bool d
 // SOCP_DUMP_COUNT (default 1) problems of the batch as text, one file per
 // quantity, as the reference's commented-out dumps do (solver.jl:48-67: A, G,
 // c, b, h, cones; :75-82: the init right-hand side initv = [-c; b; h]).
+// A QP solve (socp_batch_solve_qp) also writes its P.
 // Matrices are written one row per line.  Diagnostic only: it synchronises.
 static void dump_mat(const char* dir, int64_t p, const char* name, const double* v, int rows, int cols) {
   char fn[1024];
@@ -509,7 +516,7 @@ static void dump_mat(const char* dir, int64_t p, const char* name, const double*
   }
   fclose(f);
 }
-static int dump_problems(socp_ctx* ctx, const SmallArgs& a) {
+static int dump_problems(socp_ctx* ctx, const SmallArgs& a, const double* Pq = nullptr) {
   const char* dir = getenv("SOCP_DUMP_DIR");
   if (!dir || !*dir) return 0;
   const char* cnt = getenv("SOCP_DUMP_COUNT");
@@ -540,6 +547,11 @@ static int dump_problems(socp_ctx* ctx, const SmallArgs& a) {
     dump_mat(dir, p, "b", b, m, 1);
     dump_mat(dir, p, "h", h, k, 1);
     dump_mat(dir, p, "initv", iv, n + m + k, 1);
+    if (Pq) {
+      std::vector<double> pb((size_t)n * n);
+      HIPCHK(hipMemcpy(pb.data(), Pq + pm * (int64_t)n * n, sizeof(double) * n * n, hipMemcpyDefault));
+      dump_mat(dir, p, "P", pb.data(), n, n);
+    }
     char fn[1024];
     snprintf(fn, sizeof(fn), "%s/problem%lld_cones.txt", dir, (long long)p);
     if (FILE* f = fopen(fn, "w")) {
@@ -551,12 +563,14 @@ static int dump_problems(socp_ctx* ctx, const SmallArgs& a) {
   return 0;
 }
 
-extern "C" int socp_batch_solve_ex(socp_ctx* ctx, const socp_dims* dims, const int32_t* cone_kind,
-                                   const int32_t* cone_offs, const int32_t* cone_dim,
-                                   const double* c, const double* A, const double* b,
-                                   const double* G, const double* h, const uint8_t* sing,
-                                   const socp_params* params, double* x, double* y, double* z,
-                                   double* s, int32_t* iters, int32_t* status, double* res) {
+// socp_batch_solve_ex, and with Pm != NULL socp_batch_solve_qp: the QP solver
+// kernels with the objective x'Px/2 + c'x
+static int batch_solve_impl(socp_ctx* ctx, const socp_dims* dims, const int32_t* cone_kind,
+                            const int32_t* cone_offs, const int32_t* cone_dim, const double* Pm,
+                            const double* c, const double* A, const double* b,
+                            const double* G, const double* h, const uint8_t* sing,
+                            const socp_params* params, double* x, double* y, double* z,
+                            double* s, int32_t* iters, int32_t* status, double* res) {
   if (!ctx) return fail(SOCP_E_INVALID, "ctx is NULL");
   SmallArgs a;
   memset(&a, 0, sizeof(a));
@@ -570,11 +584,21 @@ extern "C" int socp_batch_solve_ex(socp_ctx* ctx, const socp_dims* dims, const i
   const int64_t B = dims->batch;
   const int n = dims->n, m = dims->m, k = dims->k;
   TRY(check_detect_flags(P.flags));
+  const bool qp = Pm != nullptr;
+  if (qp && (P.flags & SOCP_F_EXPLICIT_INVERSE))
+    return fail(SOCP_E_UNSUPPORTED,
+                "socp_batch_solve_qp with SOCP_F_EXPLICIT_INVERSE: no QP kernel is compiled in the explicit-inverse "
+                "operation order");
+  if (qp && (P.flags & SOCP_F_DETECT_INFEASIBLE))
+    return fail(SOCP_E_UNSUPPORTED,
+                "socp_batch_solve_qp with SOCP_F_DETECT_INFEASIBLE: the unboundedness rule would also need Px = 0, "
+                "which the detecting kernels do not test");
   if (B == 0) return 0;
   if (!c || !G || !h || !x || !z || !s || !iters || !status || (m > 0 && (!A || !b || !y)))
     return fail(SOCP_E_INVALID, "NULL data pointer");
   const bool force_large = (P.flags & SOCP_F_FORCE_LARGE) != 0;
   const SmallVariant* v = (force_large || dims->ncones > NCS) ? nullptr : pick_variant(n, m, k);
+  if (qp && v && !v->qp_kernel) v = nullptr;  // no QP instantiation of the shape: the blocked kernel
   if (!v && !large_fits(n, m, k, dims->ncones, nullptr, nullptr, (P.flags & SOCP_F_EXPLICIT_INVERSE) != 0))
     return fail(SOCP_E_UNSUPPORTED, kUnsupported);
   HIPCHK(hipSetDevice(ctx->device));
@@ -603,6 +627,11 @@ extern "C" int socp_batch_solve_ex(socp_ctx* ctx, const socp_dims* dims, const i
   TRY(stage_in(ctx, X::B_G, G, MB * k * n, dev, &a.G));
   TRY(stage_in(ctx, X::B_H, h, (size_t)B * k, dev, &a.h));
   TRY(stage_in(ctx, X::B_SING, sing, MB, dev, &a.sing));
+  const double* Pd = nullptr;
+  if (qp) {
+    TRY(stage_in(ctx, X::B_P, Pm, MB * n * n, dev, &Pd));
+    small_set_qp(a, Pd);
+  }
   TRY(stage_out(ctx, X::B_X, x, (size_t)B * n, dev, warm, &a.x));
   TRY(stage_out(ctx, X::B_Y, y, (size_t)B * m, dev, warm, &a.y));
   TRY(stage_out(ctx, X::B_Z, z, (size_t)B * k, dev, warm, &a.z));
@@ -612,8 +641,8 @@ extern "C" int socp_batch_solve_ex(socp_ctx* ctx, const socp_dims* dims, const i
   TRY(stage_out(ctx, X::B_RES, res, (size_t)B * 3, dev, false, &a.res));
   if (ctx->buf[X::B_CNT].ensure(256)) return fail(SOCP_E_NOMEM, "device allocation failed");
   a.counter = (int32_t*)ctx->buf[X::B_CNT].p;
-  TRY(dump_problems(ctx, a));
-  TRY(v ? launch_small(ctx, a, v) : launch_large(ctx, a));
+  TRY(dump_problems(ctx, a, Pd));
+  TRY(v ? launch_small(ctx, a, v, qp) : launch_large(ctx, a, nullptr, qp));
   TRY(copy_back(ctx, x, a.x, (size_t)B * n, dev));
   TRY(copy_back(ctx, y, a.y, (size_t)B * m, dev));
   TRY(copy_back(ctx, z, a.z, (size_t)B * k, dev));
@@ -623,6 +652,26 @@ extern "C" int socp_batch_solve_ex(socp_ctx* ctx, const socp_dims* dims, const i
   TRY(copy_back(ctx, res, a.res, (size_t)B * 3, dev));
   if (!dev) HIPCHK(hipStreamSynchronize(ctx->stream));
   return 0;
+}
+
+extern "C" int socp_batch_solve_ex(socp_ctx* ctx, const socp_dims* dims, const int32_t* cone_kind,
+                                   const int32_t* cone_offs, const int32_t* cone_dim,
+                                   const double* c, const double* A, const double* b,
+                                   const double* G, const double* h, const uint8_t* sing,
+                                   const socp_params* params, double* x, double* y, double* z,
+                                   double* s, int32_t* iters, int32_t* status, double* res) {
+  return batch_solve_impl(ctx, dims, cone_kind, cone_offs, cone_dim, nullptr, c, A, b, G, h, sing, params, x, y, z,
+                          s, iters, status, res);
+}
+
+extern "C" int socp_batch_solve_qp(socp_ctx* ctx, const socp_dims* dims, const int32_t* cone_kind,
+                                   const int32_t* cone_offs, const int32_t* cone_dim, const double* P,
+                                   const double* c, const double* A, const double* b,
+                                   const double* G, const double* h, const uint8_t* sing,
+                                   const socp_params* params, double* x, double* y, double* z,
+                                   double* s, int32_t* iters, int32_t* status, double* res) {
+  return batch_solve_impl(ctx, dims, cone_kind, cone_offs, cone_dim, P, c, A, b, G, h, sing, params, x, y, z, s,
+                          iters, status, res);
 }
 
 extern "C" int socp_batch_solve(socp_ctx* ctx, const socp_dims* dims, const int32_t* cone_kind,

@@ -25,6 +25,9 @@ struct SmallVariant {
   // the plain solver compiled for pure slots (KM = SLOT_PAIR_* << 4; two-slot
   // shapes, NP > 16, else NULL): [SLOT_PAIR_* - 1]
   const void* slot_kernel[4];
+  // socp_batch_solve_qp (KM 8): the solver with the quadratic term P, mixed slots
+  const void* qp_kernel;
+  const char* qp_name;
 };
 
 // table of compiled register-resident variants, ordered by (NQ, NP, MQ)
@@ -114,7 +117,8 @@ struct LargeArgs {
 // gv: the problem's vectors in the HBM workspace instead of LDS (shapes whose
 // vectors exceed a CU's 160 KiB of LDS)
 // di: the solver with the infeasibility rule (SOCP_F_DETECT_INFEASIBLE; not with xi)
-const void* large_kernel_ptr(bool xi, bool gv, bool di = false);
-const char* large_kernel_name(bool xi, bool gv, bool di = false);
+// qp: the solver with the quadratic term P (socp_batch_solve_qp; with neither xi nor di)
+const void* large_kernel_ptr(bool xi, bool gv, bool di = false, bool qp = false);
+const char* large_kernel_name(bool xi, bool gv, bool di = false, bool qp = false);
 
 }  // namespace socp

@@ -170,8 +170,19 @@ __device__ __forceinline__ d4 tile_mm(const d4& U, const d4& V, d4 C) {
 // instead of the triangular solves against H = L L'.
 // GV: the vectors in global memory (LV above).
 // DI: the solver with the infeasibility rule (SOCP_F_DETECT_INFEASIBLE).
-template <bool XI, bool GV, bool DI = false>
-struct Large {
+// QP: the objective is x'Px/2 + c'x (socp_batch_solve_qp): H = P + G'W^-2 G
+// (+A'A), rd = Px + A'y + G'z + c; P is read from the caller's array.
+// (Its state is a base class that is empty for the linear kernels: a Large is
+// a stack object that the out-of-line members address, and a member more would
+// move every offset in them.)
+template <bool QP>
+struct LargeQp {};
+template <>
+struct LargeQp<true> {
+  __attribute__((address_space(1))) const double* Pq = nullptr;  // this problem's P (n x n, column-major)
+};
+template <bool XI, bool GV, bool DI = false, bool QP = false>
+struct Large : LargeQp<QP> {
   static constexpr bool CHOL = SOCP_LG_CHOL && !XI;
   // where Li = H^-1 is formed (XI, and every shape of a SOCP_LG_CHOL=0 build):
   // from the Cholesky factor, Li = L^-T L^-1 (chol_inverse), as
@@ -1352,6 +1363,15 @@ struct Large {
     BAR();
   }
 
+  // QP: H += P on what form_H / form_H_staged stored and the factorisation
+  // reads -- the 16x16 tiles on and below the diagonal, rows and columns < n
+  // (the identity padding stays).  A wavefront per column, lanes along its rows.
+  __device__ void add_P() {
+    for (int c = wv; c < n; c += NW)
+      for (int r = (c & ~15) + lane; r < n; r += 64) Hm[(int64_t)c * L.NPAD + r] += this->Pq[(int64_t)c * n + r];
+    BAR();
+  }
+
   // One panel of the sweep below by 16x16 tiles on MFMA: the 64 rank-1 pivot
   // steps regrouped into a tile Cholesky of the pivot block.  With D = M_PP =
   // L L' (tile rows t = 0..3 of the panel; W_t = L_tt^-1 by factor_tile, whose
@@ -2162,6 +2182,9 @@ struct Large {
       else
         form_H(addAA);
     }
+    // (h_only: the sing probe, cholesky(G'G) -- without P)
+    if constexpr (QP)
+      if (!h_only) add_P();
     LSTAMP(SP_SYRK);
     if constexpr (CHOL) {
     if (!chol(Hm, L.NPAD)) return ST_CHOL_H;
@@ -2527,14 +2550,20 @@ struct Large {
     LDS_BAR();
   }
 
-  // rd = A'y + G'z + c, rp = Ax - b, rz = Gx + s - h (solver.jl:109-118)
+  // rd = A'y + G'z + c (QP: + Px), rp = Ax - b, rz = Gx + s - h (solver.jl:109-118)
   __device__ void residuals(double& nd, double& np_, double& gap) {
     bool merged = false;
     for (int rep = 0; rep < LREP(64); ++rep) merged = gemv_GtG(Z_, TN, X_, S_, H_, DZ);  // G'z and Gx + s - h in one G pass
     if (!merged) gemv_Gt(Z_, TN, -1);
     double d2 = 0.0;
     for (int j = tid; j < n; j += NTH) {
-      const double v = (At_dot(Y_, j) + LV(TN + j)) + LV(C_ + j);
+      double v = (At_dot(Y_, j) + LV(TN + j)) + LV(C_ + j);
+      if constexpr (QP) {  // + (Px)_j = sum_i P(j, i) x_i: the threads of a wavefront read along a column of P
+        double px = 0.0;
+#pragma unroll 8
+        for (int i = 0; i < n; ++i) px = fma(this->Pq[(int64_t)i * n + j], LV(X_ + i), px);
+        v += px;
+      }
       LV(RD + j) = v;
       d2 = fma(v, v, d2);
     }
@@ -2627,6 +2656,7 @@ struct Large {
   __device__ void run(int64_t p) {
     LSTAMP(SP_OTHER);
     if (rec0) set_record(p);
+    if constexpr (QP) this->Pq = (gcdbl*)small_qp(a) + ((a.flags & F_SHARED) ? 0 : p * (int64_t)n * n);
     load(p);
     LSTAMP(SP_LOAD);
     int status = ST_MAXIT, iters = 0;
@@ -2862,13 +2892,13 @@ struct Large {
   }
 };
 
-template <bool XI, bool GV, bool DI = false>
+template <bool XI, bool GV, bool DI = false, bool QP = false>
 __global__ void __launch_bounds__(NTH, 1) socp_large_kernel(LargeArgs args) {
   // the next problem index lives in dynamic LDS (slot 63 of the block-reduction
   // area; GV: slot 0 of the kernel's small LDS): no static LDS, so lg_lds
   // starts at LDS address 0 and the staged SYRK's DMA buffers lie in the
   // first 64 KiB
-  Large<XI, GV, DI> S(args);
+  Large<XI, GV, DI, QP> S(args);
   S.init_tables();
   const int pslot = GV ? 0 : S.L.o_red + 63;
   while (true) {
@@ -2882,7 +2912,12 @@ __global__ void __launch_bounds__(NTH, 1) socp_large_kernel(LargeArgs args) {
   S.flush_stamps();
 }
 
-#if SOCP_LG_GV_TU
+#if SOCP_LG_QP_TU
+// the QP kernels (socp_large_qp.o: this file with SOCP_LG_QP_TU=1)
+template __global__ void socp_large_kernel<false, false, false, true>(LargeArgs);
+template __global__ void socp_large_kernel<false, true, false, true>(LargeArgs);
+}  // namespace lg
+#elif SOCP_LG_GV_TU
 // the global-vector kernels (socp_large_gv.o: this file with SOCP_LG_GV_TU=1)
 template __global__ void socp_large_kernel<false, true>(LargeArgs);
 template __global__ void socp_large_kernel<true, true>(LargeArgs);
@@ -2892,16 +2927,23 @@ template __global__ void socp_large_kernel<false, true, true>(LargeArgs);
 extern template __global__ void socp_large_kernel<false, true>(LargeArgs);
 extern template __global__ void socp_large_kernel<true, true>(LargeArgs);
 extern template __global__ void socp_large_kernel<false, true, true>(LargeArgs);
+extern template __global__ void socp_large_kernel<false, false, false, true>(LargeArgs);
+extern template __global__ void socp_large_kernel<false, true, false, true>(LargeArgs);
 }  // namespace lg
 
-const void* large_kernel_ptr(bool xi, bool gv, bool di) {
+const void* large_kernel_ptr(bool xi, bool gv, bool di, bool qp) {
+  if (qp)
+    return (xi || di) ? nullptr
+                      : (gv ? (const void*)&lg::socp_large_kernel<false, true, false, true>
+                            : (const void*)&lg::socp_large_kernel<false, false, false, true>);
   if (di && !xi)
     return gv ? (const void*)&lg::socp_large_kernel<false, true, true>
               : (const void*)&lg::socp_large_kernel<false, false, true>;
   if (gv) return xi ? (const void*)&lg::socp_large_kernel<true, true> : (const void*)&lg::socp_large_kernel<false, true>;
   return xi ? (const void*)&lg::socp_large_kernel<true, false> : (const void*)&lg::socp_large_kernel<false, false>;
 }
-const char* large_kernel_name(bool xi, bool gv, bool di) {
+const char* large_kernel_name(bool xi, bool gv, bool di, bool qp) {
+  if (qp) return gv ? "socp_large_qp_gv_kernel" : "socp_large_qp_kernel";
   if (di && !xi) return gv ? "socp_large_di_gv_kernel" : "socp_large_di_kernel";
   if (gv) return xi ? "socp_large_xi_gv_kernel" : "socp_large_gv_kernel";
   return xi ? "socp_large_xi_kernel" : "socp_large_kernel";

@@ -168,6 +168,13 @@ __device__ __forceinline__ double small_itol(const SmallArgs& a) {
   return __longlong_as_double(static_cast<long long>(reinterpret_cast<uintptr_t>(a.dx)));
 }
 
+// The QP solver kernels (socp_batch_solve_qp; KM bit 3, the blocked kernel's
+// QP instantiations): MODE_SOLVE reads no dy either, and that slot carries P --
+// B matrices n x n column-major, or one with F_SHARED.  Only those kernels read
+// it; the argument layout of the others stays as it was.
+inline void small_set_qp(SmallArgs& a, const double* P) { a.dy = P; }
+__device__ __forceinline__ const double* small_qp(const SmallArgs& a) { return a.dy; }
+
 // ------------------------------------------------------------ LDS layout
 // Fixed region (independent of the template shape):
 #ifdef SOCP_DIAG
@@ -958,7 +965,10 @@ __device__ __forceinline__ void factor_tile(d4 Dt, d4& W, bool& ok, const H& hoo
 // Mixed (every kernel but the pure-slot solver kernels of the two-slot
 // shapes): the fixed layout, slot s, lane l = element 64 s + l, and cone ops
 // that handle any element.  Pure: SmallArgs::slot_rot is honoured.
-template <int NQ, int NP, int MQ, bool XI = false, int KS0 = SLOT_MIXED, int KS1 = SLOT_MIXED>
+// QP: the objective is x'Px/2 + c'x (socp_batch_solve_qp): H = P + G'W^-2 G
+// (+A'A) and rd = Px + A'y + G'z + c; P is streamed from global memory (add_P,
+// P_mv), never resident.
+template <int NQ, int NP, int MQ, bool XI = false, int KS0 = SLOT_MIXED, int KS1 = SLOT_MIXED, bool QP = false>
 struct Small {
   using SH = Shape<NQ, NP, MQ>;
   static_assert((KS0 == SLOT_MIXED) == (KS1 == SLOT_MIXED), "both slots pure or both mixed");
@@ -1724,6 +1734,8 @@ struct Small {
       zv[t] = LDS(Z_ + 64 * t + lane);
       sv[t] = LDS(S_ + 64 * t + lane);
     }
+    double pq[NQ];  // QP: (P x)[16q+cl], formed first, while few registers are live
+    if constexpr (QP) P_mv(X_, pq);
     // ---- scaling, first reduction: |z_1|^2, |s_1|^2, z_1's_1 per cone
     double v[2][3], zi[2], si[2];
 #pragma unroll
@@ -1785,7 +1797,8 @@ struct Small {
       for (int q = 0; q < NQ; ++q) {
         const int j = 16 * q + cl;
         if (j < n) {
-          const double vv = (at[q] + acc[q]) + cq[q];
+          double vv = (at[q] + acc[q]) + cq[q];
+          if constexpr (QP) vv += pq[q];
           LDS(RD + j) = -vv;  // the residuals are stored negated: the affine RHS (solver.jl:124)
           d2 = fma(vv, vv, d2);
         }
@@ -2319,6 +2332,78 @@ struct Small {
       for (int q = 0; q < NQ; ++q) X[q] = fma(c.ca, gr[q], c.cb * u[q]);
     }
   }
+  // ---------------------------------------------------------------- QP
+  // This problem's P (set by run()) and the byte range form_H may read of it:
+  // n n 8, or 0 for MP_SINGTEST's G'G, whose loads then all return 0.
+  const double* qp_P = nullptr;
+  int qp_hrange = 0;
+  // raw buffer over P: an element outside n x n takes an offset past the range
+  // and reads 0 (load_problem's G descriptor does the same)
+  __device__ __forceinline__ __amdgpu_buffer_rsrc_t qp_rsrc(int range) const {
+    const uint64_t pu = (uint64_t)qp_P;
+    const uint64_t base = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(pu >> 32)) << 32) |
+                          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)pu);
+    return __builtin_amdgcn_make_buffer_rsrc((void*)base, (short)0, __builtin_amdgcn_readfirstlane(range), 0x00020000);
+  }
+  // T += P, tile by tile in the tiles' own layout: lane (g, cl), register r of
+  // block (bi, bj) holds row 16 bi + g + 4r, column 16 bj + cl.  P is symmetric,
+  // so the element is read as P(column, row): 16 lanes read 128 contiguous bytes.
+  __device__ __forceinline__ void add_P() {
+    LANE_IDS();
+    const __amdgpu_buffer_rsrc_t rs = qp_rsrc(qp_hrange);
+#pragma unroll
+    for (int ti = 0; ti < NQ; ++ti)
+#pragma unroll
+      for (int tj = 0; tj <= ti; ++tj) {
+        const int bi = UPPER_H ? tj : ti, bj = UPPER_H ? ti : tj;
+        const int Cc = 16 * bj + cl;
+        double pv[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int R = 16 * bi + g + 4 * r;
+          const int off = (R < n && Cc < n) ? (R * n + Cc) * 8 : 0x40000000;
+          pv[r] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, 0));
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) T[tri(ti, tj)][r] += pv[r];
+        // two tiles' loads per round trip: the registers the loads hold stay bounded (<4,24,1> is at the cap)
+        if (tri(ti, tj) % 2 == 1) SCHED_FENCE();
+      }
+  }
+  // acc[q] (all lanes) = (P v)[16q+cl], v an n-vector in LDS: rows split over
+  // the 4 lane groups as in At_mv; row i of P is read as its column i
+  __device__ __forceinline__ void P_mv(int v, double (&acc)[NQ]) {
+    LANE_IDS();
+    const __amdgpu_buffer_rsrc_t rs = qp_rsrc(n * n * (int)sizeof(double));
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) acc[q] = 0.0;
+    // PB row steps (of 4 NQ), up to 16 loads, per round trip (At_mv's batching)
+    constexpr int PB = NQ == 2 ? 8 : 4;
+    static_assert((4 * NQ) % PB == 0, "whole batches");
+#pragma unroll
+    for (int s0 = 0; s0 < NQ * 4; s0 += PB) {
+      double vi[PB], pv[PB][NQ];
+#pragma unroll
+      for (int s = 0; s < PB; ++s) {
+        const int i = g + 4 * (s0 + s);
+        vi[s] = i < n ? LDS(v + i) : 0.0;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+          const int j = 16 * q + cl;
+          const int off = (i < n && j < n) ? (i * n + j) * 8 : 0x40000000;
+          pv[s][q] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, 0));
+        }
+      }
+      SCHED_FENCE();
+#pragma unroll
+      for (int s = 0; s < PB; ++s)
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) acc[q] = fma(pv[s][q], vi[s], acc[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) acc[q] = rows_sum(acc[q]);
+  }
+
   static constexpr bool diag_tile(int t) {
     for (int i = 0; i < NQ; ++i)
       if (tri(i, i) == t) return true;
@@ -2426,6 +2511,7 @@ struct Small {
             for (int tj = 0; tj <= ti; ++tj) T[tri(ti, tj)] = UPPER_H ? mfma(Aq[tj], Aq[ti], T[tri(ti, tj)]) : mfma(Aq[ti], Aq[tj], T[tri(ti, tj)]);
         }
     }
+    if constexpr (QP) add_P();
 #pragma unroll
     for (int ti = 0; ti < NQ; ++ti)
 #pragma unroll
@@ -3463,7 +3549,7 @@ struct Small {
     return sq;
   }
 
-  // rd = A'y + G'z + c, rp = Ax - b, rz = Gx + s - h (solver.jl:109-118)
+  // rd = A'y + G'z + c (QP: + Px), rp = Ax - b, rz = Gx + s - h (solver.jl:109-118)
   __device__ __forceinline__ void residuals(double& nd, double& np_, double& gap) {
     MARK_BEGIN("residuals");
     LANE_IDS();
@@ -3482,6 +3568,8 @@ struct Small {
       zv[t] = LDS(Z_ + 64 * t + lane);
       sv[t] = LDS(S_ + 64 * t + lane);
     }
+    double pq[NQ];  // QP: (P x)[16q+cl], formed first, while few registers are live
+    if constexpr (QP) P_mv(X_, pq);
     if (SOCP_KO & 32) {
       for (int q = 0; q < NQ; ++q) acc[q] = 0.0;
     } else {
@@ -3498,7 +3586,8 @@ struct Small {
       for (int q = 0; q < NQ; ++q) {
         const int j = 16 * q + cl;
         if (j < n) {
-          const double v = (at[q] + acc[q]) + cq[q];
+          double v = (at[q] + acc[q]) + cq[q];
+          if constexpr (QP) v += pq[q];
           LDS(RD + j) = -v;  // the residuals are stored negated: the affine RHS (solver.jl:124)
           d2 = fma(v, v, d2);
         }
@@ -3784,6 +3873,10 @@ struct Small {
     double isc = 1.0;  // DI: the certificate's factor
     int after_singtest;
     bool have_sing = false;
+    if constexpr (QP) {
+      qp_P = small_qp(a) + ((a.flags & F_SHARED) ? 0 : p * (int64_t)n * n);
+      qp_hrange = n * n * (int)sizeof(double);
+    }
     if (mode == MODE_SOLVEKKT) {  // setup_iter failed for this problem: NaN solution, its status
       const int st0 = (int)uni(a.rec[p * a.rec_stride + REC_STATUS]);
       if (st0) {
@@ -3855,6 +3948,7 @@ struct Small {
       switch (phase) {
         case MP_SINGTEST:  // Problem's `sing` (Socp.jl:49-56): is G'G positive definite?
           MARK_BEGIN("case MP_SINGTEST");
+          if constexpr (QP) qp_hrange = 0;  // cholesky(G'G): without P
           scaling_identity();
           fac_kind = FAC_IDENT;
           fac_aa = false;
@@ -3864,6 +3958,7 @@ struct Small {
         case MP_SINGTEST_POST:
           MARK_BEGIN("case MP_SINGTEST_POST");
           sing = (fst == ST_CHOL_H);
+          if constexpr (QP) qp_hrange = n * n * (int)sizeof(double);
           next = after_singtest;
           break;
         case MP_FACTOR:  // setup_iter (densesolver.jl:41-52)
@@ -4113,13 +4208,14 @@ struct Small {
 // KM bits 4..: the pure-slot solver kernels (KM = SLOT_PAIR_* << 4, plain solver only);
 // KM bit 0: the plugin-entry kernel (MODE_KKT / MODE_SETUP / MODE_SOLVEKKT)
 // instead of the solver; bit 1: the explicit-inverse variant (XI above);
-// bit 2 (KM = 4): the solver with SOCP_F_DETECT_INFEASIBLE
+// bit 2 (KM = 4): the solver with SOCP_F_DETECT_INFEASIBLE;
+// bit 3 (KM = 8): the QP solver (socp_batch_solve_qp), mixed slots only
 template <int NQ, int NP, int MQ, int KM>
 #ifndef SOCP_DEV_MINW
 #define SOCP_DEV_MINW 1  // probe builds only: waves per SIMD the register allocation must allow
 #endif
 __global__ void __launch_bounds__(64, (KM & 3) == 0 ? SOCP_DEV_MINW : 1) socp_small_kernel(SmallArgs args) {
-  Small<NQ, NP, MQ, (KM & 2) != 0, slot_pair_kind(KM >> 4, 0), slot_pair_kind(KM >> 4, 1)> S(args);
+  Small<NQ, NP, MQ, (KM & 2) != 0, slot_pair_kind(KM >> 4, 0), slot_pair_kind(KM >> 4, 1), (KM & 8) != 0> S(args);
   S.init_tables();
   STAMP_START_S(S);
   while (true) {

@@ -137,7 +137,7 @@ def _check_sizes(B, **arrays):
 
 def batch_solve(cones, n, m, k, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5, step=0.99,
                 sigma_exp=3, init_eps=1e-10, warm=None, ctx=None, res=False, out=None, force_large=False,
-                explicit_inverse=False, detect_infeasible=False, shared_matrices=False):
+                explicit_inverse=False, detect_infeasible=False, shared_matrices=False, P=None):
     """Solve a batch of independent problems (same dims and cone structure).
 
     Arrays follow include/socp.h: per-problem column-major A (m x n), G (k x n)
@@ -158,6 +158,14 @@ def batch_solve(cones, n, m, k, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5,
     m x n matrix, G ONE k x n matrix and sing ONE byte (or None), used by every
     problem; c, b, h stay per problem.  The outputs are bitwise those of the
     same call on A, G and sing replicated B times.
+    P (socp_batch_solve_qp): a quadratic objective x'Px/2 + c'x -- per problem
+    an n x n symmetric positive semidefinite matrix, column-major, stacked
+    batch-major (ONE matrix with shared_matrices).  Host arrays are checked
+    for symmetry (ValueError); torch tensors are used in place, unchecked.
+    The dual residual becomes Px + A'y + G'z + c and H = P + G'W^-2 G; a P
+    that makes H indefinite gives that problem CHOL_H_FAILED.  Not together
+    with explicit_inverse or detect_infeasible (SOCP_E_UNSUPPORTED).  P=None
+    is the plain call.
     Returns dict(x, y, z, s, iters, status[, res]).
     """
     L = _lib.load()
@@ -167,7 +175,15 @@ def batch_solve(cones, n, m, k, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5,
         raise ValueError(f"c: {_size(c)} elements is not a multiple of n={n}")
     MB = 1 if shared_matrices else B
     _check_sizes(B, A=(A if m else None, MB * m * n), b=(b if m else None, B * m), G=(G, MB * k * n),
-                 h=(h, B * k), sing=(sing, MB))
+                 h=(h, B * k), sing=(sing, MB), P=(P, MB * n * n))
+    if P is not None and (_is_torch(P) != _is_torch(G) or (_is_torch(P) and (
+            str(P.dtype) != "torch.float64" or P.device != G.device or not P.is_contiguous()))):
+        raise ValueError("P must be on the same side as G (host array, or contiguous float64 tensor on G's device)")
+    if P is not None and not _is_torch(P):
+        Ph = _host(P).reshape(MB, n, n)
+        if not np.allclose(Ph, Ph.transpose(0, 2, 1)):
+            raise ValueError("P: every problem's matrix must be symmetric")
+        P = Ph.reshape(-1)
     if warm is not None:
         wx, wy, wz, ws = warm
         _check_sizes(B, warm_x=(wx, B * n), warm_y=(wy if m else None, B * m), warm_z=(wz, B * k),
@@ -186,8 +202,8 @@ def batch_solve(cones, n, m, k, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5,
         flags |= F_DETECT_INFEASIBLE
     if shared_matrices:
         flags |= F_SHARED_MATRICES
-    P = default_params(maxit=maxit, tol=tol, step=step, sigma_exp=sigma_exp, init_eps=init_eps,
-                       flags=flags)
+    pr = default_params(maxit=maxit, tol=tol, step=step, sigma_exp=sigma_exp, init_eps=init_eps,
+                        flags=flags)
     if dev:
         import torch
         devc = G.device
@@ -219,11 +235,15 @@ def batch_solve(cones, n, m, k, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5,
         arrs = dict(c=_host(c), A=_host(A) if m else None, b=_host(b) if m else None, G=_host(G),
                     h=_host(h), sing=_host(sing, np.uint8) if sing is not None else None)
     p = _lib.ptr
-    rc = L.socp_batch_solve_ex(
-        ctx.handle, dims, p(kind), p(offs), p(dim), p(arrs["c"]), p(arrs["A"] if m else None),
-        p(arrs["b"] if m else None), p(arrs["G"]), p(arrs["h"]), p(arrs["sing"]), P,
-        p(out["x"]), p(out["y"] if m else None), p(out["z"]), p(out["s"]), p(out["iters"]),
-        p(out["status"]), p(out.get("res")))
+    head = (ctx.handle, dims, p(kind), p(offs), p(dim))
+    tail = (p(arrs["c"]), p(arrs["A"] if m else None),
+            p(arrs["b"] if m else None), p(arrs["G"]), p(arrs["h"]), p(arrs["sing"]), pr,
+            p(out["x"]), p(out["y"] if m else None), p(out["z"]), p(out["s"]), p(out["iters"]),
+            p(out["status"]), p(out.get("res")))
+    if P is None:
+        rc = L.socp_batch_solve_ex(*head, *tail)
+    else:
+        rc = L.socp_batch_solve_qp(*head, p(P), *tail)
     _lib.check(rc)
     if not dev and m == 0:
         out["y"] = out["y"][:0]
@@ -673,9 +693,11 @@ def _colmajor(M, rows, cols):
 
 class Problem:
     """Problem(c, A, b, G, h, cones) (Socp.jl:40-59).  `sing` is true when
-    cholesky(G'G) throws, exactly the reference's rule (Socp.jl:49-56)."""
+    cholesky(G'G) throws, exactly the reference's rule (Socp.jl:49-56).
+    P (optional, n x n symmetric positive semidefinite): the objective is
+    x'Px/2 + c'x (``batch_solve``'s P); `sing` never sees it."""
 
-    def __init__(self, c, A, b, G, h, cones):
+    def __init__(self, c, A, b, G, h, cones, P=None):
         c = np.asarray(c, dtype=np.float64).reshape(-1)
         n = len(c)
         A = np.asarray(A, dtype=np.float64)
@@ -690,6 +712,10 @@ class Problem:
         k = G.shape[0]
         assert len(h) == k
         self.c, self.A, self.b, self.G, self.h = c, A, b, G, h
+        if P is not None:
+            P = np.asarray(P, dtype=np.float64)
+            assert P.shape == (n, n)
+        self.P = P
         self.cones = tuple(cones)
         self.n, self.m, self.k = n, m, k
         try:
@@ -836,7 +862,7 @@ def solve_socp(prob: Problem, ss: SolverState) -> State:
         out = batch_solve(prob.cones, prob.n, prob.m, prob.k, prob.c, _colmajor(prob.A, prob.m, prob.n),
                           prob.b, _colmajor(prob.G, prob.k, prob.n), prob.h,
                           np.array([prob.sing], np.uint8), maxit=ss.maxit, tol=ss.tol,
-                          ctx=ss.solver.ctx)
+                          ctx=ss.solver.ctx, P=None if prob.P is None else _colmajor(prob.P, prob.n, prob.n))
     ss.iters, ss.status = int(out["iters"][0]), int(out["status"][0])
     _raise_status(ss.status)
     return State(prob, out["x"], out["y"], out["z"], out["s"])
@@ -851,15 +877,21 @@ def solve_socp_batched(problems, maxit=40, tol=1e-5, ctx=None, solver="dense", d
     in ``batch_solve``: statuses PRIMAL_INFEASIBLE / DUAL_INFEASIBLE with the
     certificate in the returned state.  shared_matrices=True: a parametric
     batch -- every problem's A, G and sing must equal the first's (ValueError
-    otherwise); one copy of them goes to the device (SOCP_F_SHARED_MATRICES)."""
+    otherwise); one copy of them goes to the device (SOCP_F_SHARED_MATRICES).
+    When any problem carries a P the batch runs the QP entry (``batch_solve``'s
+    P; dense solver only); problems without one get zeros, and with
+    shared_matrices every P must equal the first's as well."""
     p0 = problems[0]
     n, m, k = p0.n, p0.m, p0.k
     for p in problems:
         assert (p.n, p.m, p.k) == (n, m, k)
     if shared_matrices:
         for i, p in enumerate(problems):
-            for name in ("A", "G"):
-                if not np.array_equal(getattr(p, name), getattr(p0, name)):
+            for name in ("A", "G", "P"):
+                if getattr(p, name) is None and getattr(p0, name) is None:
+                    continue
+                if getattr(p, name) is None or getattr(p0, name) is None or \
+                        not np.array_equal(getattr(p, name), getattr(p0, name)):
                     raise ValueError(f"shared_matrices=True: problem {i}'s {name} differs from problem 0's")
             if bool(p.sing) != bool(p0.sing):
                 raise ValueError(f"shared_matrices=True: problem {i}'s sing differs from problem 0's")
@@ -870,13 +902,18 @@ def solve_socp_batched(problems, maxit=40, tol=1e-5, ctx=None, solver="dense", d
     G = np.concatenate([_colmajor(p.G, k, n) for p in mats])
     h = np.concatenate([p.h for p in problems])
     sing = np.array([p.sing for p in mats], np.uint8)
+    P = None
+    if any(p.P is not None for p in problems):
+        if solver == "sqr":
+            raise ValueError("P: the rank-update solver takes linear objectives only")
+        P = np.concatenate([_colmajor(p.P, n, n) if p.P is not None else np.zeros(n * n) for p in mats])
     if solver == "sqr":
         out = SqrHandle(p0.cones, n, m, k, A, G, sing, ctx=ctx, shared_matrices=shared_matrices,
                         batch=len(problems)).solve_socp(
             c, b, h, maxit=maxit, tol=tol, detect_infeasible=detect_infeasible)
     else:
         out = batch_solve(p0.cones, n, m, k, c, A, b, G, h, sing, maxit=maxit, tol=tol, ctx=ctx,
-                          detect_infeasible=detect_infeasible, shared_matrices=shared_matrices)
+                          detect_infeasible=detect_infeasible, shared_matrices=shared_matrices, P=P)
     states = [State(p, out["x"][i * n:(i + 1) * n], out["y"][i * m:(i + 1) * m],
                     out["z"][i * k:(i + 1) * k], out["s"][i * k:(i + 1) * k])
               for i, p in enumerate(problems)]

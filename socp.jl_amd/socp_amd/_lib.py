@@ -37,6 +37,7 @@ EXPORTED = [
     "socp_sqr_supported", "socp_sqr_create", "socp_sqr_setup_iter", "socp_sqr_solve_kkt", "socp_sqr_factor",
     "socp_sqr_scaling", "socp_sqr_h2d_bytes", "socp_sqr_record_bytes", "socp_sqr_destroy",
     "socp_sqr_solve_socp", "socp_ctx_set_infeasibility_tol", "socp_debug_slot_plan",
+    "socp_batch_solve_qp",
 ]
 
 OUTCOME_BYTES = 32  # sizeof(socp_outcome): int32 status, int32 iters, double rd, rp, gap
@@ -106,6 +107,7 @@ def load():
     common = [vp, C.POINTER(Dims), i32p, i32p, i32p]
     L.socp_batch_solve.argtypes = common + [dp] * 5 + [u8p, C.POINTER(Params)] + [dp] * 4 + [i32p, i32p]
     L.socp_batch_solve_ex.argtypes = common + [dp] * 5 + [u8p, C.POINTER(Params)] + [dp] * 4 + [i32p, i32p, dp]
+    L.socp_batch_solve_qp.argtypes = common + [dp] * 6 + [u8p, C.POINTER(Params)] + [dp] * 4 + [i32p, i32p, dp]
     L.socp_batch_kkt_solve.argtypes = common + [dp, dp, u8p] + [dp] * 2 + [dp] * 4 + [dp] * 4 + [i32p, C.c_int32]
     L.socp_generate.argtypes = common + [C.c_uint64, C.c_int64] + [dp] * 5
     L.socp_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
