@@ -362,6 +362,14 @@ static bool fuse_u_enabled() {
   return !(e && e[0] == '0' && e[1] == '\0');
 }
 
+// SOCP_INIT_OVERLAP=0 (env, read at every launch): the initial point's G'G is
+// formed by form_H's row loop on every kernel, not under G's load in
+// load_problem (the A/B of the overlap; the results are the same bits)
+static bool init_overlap_enabled() {
+  const char* e = getenv("SOCP_INIT_OVERLAP");
+  return !(e && e[0] == '0' && e[1] == '\0');
+}
+
 // qp: the QP solver (socp_batch_solve_qp; args carries P, small_set_qp)
 static int launch_small(socp_ctx* ctx, SmallArgs& args, const SmallVariant* v, bool qp = false) {
   args.al_rows = cone_rows_uniform(args.cones, args.nc);
@@ -397,6 +405,10 @@ static int launch_small(socp_ctx* ctx, SmallArgs& args, const SmallVariant* v, b
     }
   }
   if (!kern) return fail(SOCP_E_UNSUPPORTED, "no compiled kernel for these flags");
+  // the load forms the initial point's G'G: the plain solver kernels compiled with the pipelined
+  // load (mixed or pure-slot), when an initial factorisation follows the load (no warm start)
+  args.init_overlap = solver && !xi && !di && !qp && init_overlap_kernel(v->NQ, v->NP, v->MQ, 0) &&
+                      !(args.flags & SOCP_F_WARM_START) && init_overlap_enabled();
   if (lds > 64 * 1024)
     HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   int per_cu = 0;

@@ -98,6 +98,12 @@ struct SmallArgs {
   // bit 8, and bit c for every SOC cone c.  The host sets it only with al_rows >= 2,
   // cones of 32 or 64 rows (env SOCP_FUSE_U=0 clears it)
   int32_t fuse_u;
+  // nonzero: load_problem forms the initial point's G'G in the H tiles while G's
+  // loads are in flight, and the first factorisation takes it (FAC_IDENT_H).
+  // The host sets it for the plain solver kernels compiled with the pipelined
+  // load (init_overlap_kernel), never on a warm start (no initial
+  // factorisation); env SOCP_INIT_OVERLAP=0 clears it
+  int32_t init_overlap;
 };
 
 // Slot kinds.  The cone vector ops hold a k-vector as two 64-lane slots; slot
@@ -700,7 +706,25 @@ struct RSCount<C, 0> {
 // after U was formed (exit test, DomainError, infeasibility rule, the residuals
 // after the last iteration) asks for none, and nothing is carried to the
 // wave's next problem.
-enum : int { FAC_SCALED, FAC_IDENT, FAC_SCALED_U };
+// FAC_IDENT_H: the identity scaling's, with G'G already in the H tiles -- formed
+// by this problem's load_problem from the registers G's loads arrived in
+// (launches with SmallArgs::init_overlap).  Only the first factorisation after
+// that load may name it: MP_SINGTEST's, or MP_INIT's when no probe ran before it
+// (a probe factors the tiles in place, so MP_INIT behind one rebuilds H with
+// FAC_IDENT).  factor() then skips form_H's zeroing and row loop and runs the
+// rest (A'A, the padded diagonal).  Same bits as FAC_IDENT: with W = I the row
+// loop's X is fma(1.0, g, 0.0 * 0.0) = g, except that -0 becomes +0; the
+// accumulators start at +0, and a sum in round-to-nearest is -0 only when every
+// addend is, so the sign of a zero operand cannot reach H.  Per tile the MFMA
+// sequence is the same: row steps ascending from T = 0.
+enum : int { FAC_SCALED, FAC_IDENT, FAC_SCALED_U, FAC_IDENT_H };
+// The kernels compiled with the pipelined load: the plain solvers (mixed and
+// pure-slot; not the plugin entries, the explicit-inverse, detecting or QP
+// kernels) of C2's variant.  Every other instantiation keeps load_problem and
+// factor() as they were, at compile time.
+constexpr bool init_overlap_kernel(int NQ, int NP, int MQ, int KM) {
+  return NQ == 4 && NP == 24 && MQ == 1 && (KM & 15) == 0;
+}
 // driver micro-phases and solve kinds
 enum : int {
   MP_SINGTEST, MP_SINGTEST_POST, MP_FACTOR, MP_INIT, MP_ITER, MP_KKT,
@@ -1154,12 +1178,24 @@ struct Small {
   // round trips)
   bool lc_soc = false;
   int lc_off = 0, lc_dim = 0;
-  __device__ __forceinline__ void load_problem(int64_t p) {
+  // OV (init_overlap_kernel): the pipelined load.  Two batches of G stay in
+  // flight; batch b + 2 is requested, batch b (the compiler's vmcnt waits) written
+  // to the AGPRs, and on a forming load (SmallArgs::init_overlap, G really loaded)
+  // its row steps are accumulated into the H tiles straight from the registers
+  // they arrived in -- form_H's MFMAs with X = G, in its tile order, row steps
+  // ascending from T = 0 -- so the initial point's SYRK runs under the load.
+  // The LDS fill and the staging of c, b, h, A run under the first round trip.
+  // Returns whether T holds G'G: the caller hands it to run(), nothing is kept
+  // in the wave.  A resident shared G (keep_g) is not loaded, so it forms
+  // nothing; that problem's initial factorisation takes FAC_IDENT.
+  template <bool OV = false>
+  __device__ __forceinline__ bool load_problem(int64_t p) {
     MARK_BEGIN("load_problem");
     LANE_IDS();
     const bool shared = (a.flags & F_SHARED) != 0;
     const bool keep = SOCP_SHARED_RESIDENT && shared && mat_resident;  // wave-uniform
     const bool keep_g = RES_G && keep, keep_a = RES_A && keep;
+    bool formed = false;
     const double* Gp = a.G + (shared ? 0 : p * (int64_t)k * n);
     // the vectors and the first chunk of A are requested first: their HBM
     // round trip runs under G's (n, m <= 64 here, k <= 128)
@@ -1173,8 +1209,6 @@ struct Small {
     double av[AB];
 #pragma unroll
     for (int t = 0; t < AB; ++t) av[t] = (64 * t + lane < mn) ? Ap[64 * t + lane] : 0.0;
-    if (!(SOCP_KO & 1) || !ko_gloaded) {
-    ko_gloaded = true;
     // G -> AGPRs.  a_put is an asm statement the scheduler does not move loads
     // across, so the loads are issued in batches of 16 into VGPRs first (one
     // HBM round trip per batch, not per element).  Raw buffer loads over the
@@ -1198,6 +1232,24 @@ struct Small {
     int colk[NQ];  // byte offset of the lane's column in each column tile, or "out of range"
 #pragma unroll
     for (int q = 0; q < NQ; ++q) colk[q] = 16 * q + cl < n ? (16 * q + cl) * k * 8 : 0x40000000;
+    // (OV) the batches' registers: a batch is live from its request to its MFMAs, three at a time
+    constexpr int NB = OV ? GT / GB : 1;
+    uint64_t tb[NB][GB];
+    if constexpr (OV) {
+      static_assert(!OV || (RES_G && GB % NQ == 0 && GB % 4 == 0 && GT % GB == 0 && NB >= 2 && !(SOCP_KO & 1)),
+                    "whole batches of whole row steps");
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int t = 0; t < GB; ++t) {
+          const int e = b * GB + t;
+          const int row = 4 * (e / NQ) + g;
+          const int off = row < k ? colk[e % NQ] + row * 8 : 0x40000000;
+          tb[b][t] = __builtin_bit_cast(uint64_t, __builtin_amdgcn_raw_buffer_load_b64(grs, off, 0, 0));
+        }
+      SCHED_FENCE();
+    } else if (!(SOCP_KO & 1) || !ko_gloaded) {
+    ko_gloaded = true;
 #pragma unroll
     for (int b0 = 0; b0 < GT; b0 += GB) {
       uint64_t tmp[GB];
@@ -1242,6 +1294,16 @@ struct Small {
     if (lane < m) LDS(B_ + lane) = bv;
     if (lane < k) LDS(H_ + lane) = hv0;
     if (lane + 64 < k) LDS(H_ + 64 + lane) = hv1;
+    if constexpr (OV) {
+      // A is one chunk here, so no reload sits behind G's requests: the stores wait
+      // for the chunk alone, not for the batches in flight
+      static_assert(!OV || 256 * MQ * NQ <= 64 * AB, "A in one chunk");
+#pragma unroll
+      for (int t = 0; t < AB; ++t) {
+        const int e = 64 * t + lane;
+        if (e < mn) LDS(O_A + (e % m) * LDA + e / m) = av[t];
+      }
+    } else
     for (int e0 = 0; e0 < mn; e0 += 64 * AB) {
 #pragma unroll
       for (int t = 0; t < AB; ++t) {
@@ -1255,6 +1317,54 @@ struct Small {
       }
     }
     SYNC();
+    if constexpr (OV) {
+      // (everything above ran under the first two batches' round trip)
+      const bool form = __builtin_amdgcn_readfirstlane(a.init_overlap != 0 && !keep_g) != 0;  // wave-uniform
+      // (the lane mask again, next to its statements: they want it in SGPRs)
+      const uint32_t wm2 = (uint32_t)__builtin_amdgcn_readfirstlane(keep_g ? 0 : -1);
+      const uint64_t wmask2 = ((uint64_t)wm2 << 32) | wm2;
+      SCHED_FENCE();
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        if (b + 2 < NB) {
+#pragma unroll
+          for (int t = 0; t < GB; ++t) {
+            const int e = (b + 2) * GB + t;
+            const int row = 4 * (e / NQ) + g;
+            const int off = row < k ? colk[e % NQ] + row * 8 : 0x40000000;
+            tb[b + 2 < NB ? b + 2 : 0][t] = __builtin_bit_cast(uint64_t, __builtin_amdgcn_raw_buffer_load_b64(grs, off, 0, 0));
+          }
+        }
+        SCHED_FENCE();
+#pragma unroll
+        for (int t = 0; t < GB; t += 4) {
+          const int e = b * GB + t;
+          a_put4_masked(G[e / NQ][e % NQ], G[(e + 1) / NQ][(e + 1) % NQ], G[(e + 2) / NQ][(e + 2) % NQ],
+                        G[(e + 3) / NQ][(e + 3) % NQ], tb[b][t], tb[b][t + 1], tb[b][t + 2], tb[b][t + 3], wmask2);
+        }
+        SCHED_FENCE();
+        if (form) {
+          if (b == 0) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t) T[t] = (d4){0.0, 0.0, 0.0, 0.0};
+          }
+#pragma unroll
+          for (int r = 0; r < GB / NQ; ++r) {  // the batch's row steps, form_H's products with X = G
+            double X[NQ];
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) X[q] = __longlong_as_double((long long)tb[b][r * NQ + q]);
+#pragma unroll
+            for (int ti = 0; ti < NQ; ++ti)
+#pragma unroll
+              for (int tj = 0; tj <= ti; ++tj) T[tri(ti, tj)] = UPPER_H ? mfma(X[tj], X[ti], T[tri(ti, tj)])
+                                                                      : mfma(X[ti], X[tj], T[tri(ti, tj)]);
+          }
+        }
+        SCHED_FENCE();
+      }
+      formed = form;
+    }
+    return formed;
   }
 
   __device__ __forceinline__ double e_of(int i) const {
@@ -2409,7 +2519,9 @@ struct Small {
       if (tri(i, i) == t) return true;
     return false;
   }
-  __device__ __forceinline__ void form_H(bool addAA) {
+  // rows_in_T (FAC_IDENT_H): T already holds the row steps' sum X'X, only the
+  // rest is added
+  __device__ __forceinline__ void form_H(bool addAA, bool rows_in_T = false) {
     MARK_BEGIN("form_H");
     LANE_IDS();
     if (SOCP_KO & 65536) {  // H = I
@@ -2419,6 +2531,7 @@ struct Small {
         for (int r = 0; r < 4; ++r) T[t][r] = (diag_tile(t) && g + 4 * r == cl) ? 1.0 : 0.0;
       return;
     }
+    if (!rows_in_T) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) T[t] = (d4){0.0, 0.0, 0.0, 0.0};
 #if SOCP_SYRK_PIPE == 2
@@ -2496,6 +2609,15 @@ struct Small {
       if (pp % 2 == 1) SCHED_FENCE();
     }
 #endif
+    } else {
+      // (the tiles pass through a statement of this branch, so that whatever
+      // moves them to the row loop's registers sits here, once per problem,
+      // and not ahead of the branch on every factorisation)
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) asm volatile("" : "+v"(T[t][r]));
+    }
     if (addAA) {
 #pragma unroll
       for (int tm = 0; tm < MQ; ++tm)
@@ -2940,6 +3062,8 @@ struct Small {
   }
 
   // H (+A'A) -> sweep -> Li;  ALi' = Li A' (n x m);  S = A ALi';  S^-1.
+  // OV: a kernel with the pipelined load (the only ones that name FAC_IDENT_H)
+  template <bool OV = false>
   __device__ __forceinline__ int factor(int kind, bool addAA) {
     const bool identity = kind == FAC_IDENT;
     MARK_BEGIN("factor");
@@ -2947,7 +3071,11 @@ struct Small {
     STAMP(SP_OTHER);
     if (kind == FAC_SCALED && !(SOCP_KO & 4)) compute_U();
     STAMP(SP_U);
-    form_H(addAA);
+    if constexpr (OV) {
+      form_H(addAA, kind == FAC_IDENT_H);
+    } else {
+      form_H(addAA);
+    }
     SYNC();
     STAMP(SP_SYRK);
 #ifdef SOCP_DIAG
@@ -3859,8 +3987,10 @@ struct Small {
   // (MODE_KKT, MODE_SETUP, MODE_SOLVEKKT), compiled apart so the solver's
   // register allocation does not carry the entry paths.  DI: the solver with
   // SOCP_F_DETECT_INFEASIBLE, an instantiation of its own for the same reason.
-  template <int KM, bool DI = false>
-  __device__ __forceinline__ void run(int64_t p) {
+  // OV, h_formed: a kernel with the pipelined load, and whether this problem's
+  // load_problem left G'G in T (a value of this call, not of the wave)
+  template <int KM, bool DI = false, bool OV = false>
+  __device__ __forceinline__ void run(int64_t p, bool h_formed = false) {
     const int mode = KM ? a.mode : (a.mode == MODE_KKT ? (int)MODE_KKT : (int)MODE_SOLVE);
     STAMP(SP_LOAD);
     dbg_p = p;
@@ -3951,6 +4081,8 @@ struct Small {
           if constexpr (QP) qp_hrange = 0;  // cholesky(G'G): without P
           scaling_identity();
           fac_kind = FAC_IDENT;
+          // (the probe is a problem's first factorisation whenever it runs)
+          if constexpr (OV) fac_kind = h_formed ? FAC_IDENT_H : FAC_IDENT;
           fac_aa = false;
           fret = MP_SINGTEST_POST;
           next = MP_FACTOR;
@@ -3963,7 +4095,7 @@ struct Small {
           break;
         case MP_FACTOR:  // setup_iter (densesolver.jl:41-52)
           MARK_BEGIN("case MP_FACTOR");
-          fst = factor(fac_kind, fac_aa);
+          fst = factor<OV>(fac_kind, fac_aa);
           if (fst && fret != MP_SINGTEST_POST) {
             status = fst;
             done = true;
@@ -3981,6 +4113,8 @@ struct Small {
           }
           SYNC();
           fac_kind = FAC_IDENT;
+          // (the first factorisation only with `sing` given: a probe has factored T in place)
+          if constexpr (OV) fac_kind = (h_formed && a.sing) ? FAC_IDENT_H : FAC_IDENT;
           fac_aa = sing;
           fret = MP_SOLVE_HEAD;
           ret = RET_INIT;
@@ -4223,8 +4357,13 @@ __global__ void __launch_bounds__(64, (KM & 3) == 0 ? SOCP_DEV_MINW : 1) socp_sm
     if (threadIdx.x == 0) p = atomicAdd(args.counter, 1);
     p = __shfl(p, 0);
     if ((int64_t)p >= args.B) break;
-    S.load_problem(p);
-    S.template run<KM & 1, (KM & 4) != 0>(p);
+    if constexpr (init_overlap_kernel(NQ, NP, MQ, KM) && !(SOCP_KO & 1)) {
+      const bool h_formed = S.template load_problem<true>(p);
+      S.template run<0, false, true>(p, h_formed);
+    } else {
+      S.load_problem(p);
+      S.template run<KM & 1, (KM & 4) != 0>(p);
+    }
   }
   S.flush_stamps();
 }
