@@ -1956,7 +1956,7 @@ struct Small {
     SYNC();
 #pragma unroll
     for (int t = 0; t < NS; ++t)
-      if (64 * t + lane < k) zs += zv[t] * sv[t];
+      if (64 * t + lane < k) zs = fma(zv[t], sv[t], zs);  // (explicit: every instantiation sums z's alike, socp_batch_solve_qp's res at P = 0 included)
     double r3[3] = {d2, p2, zs};  // the three whole-wave sums in one interleaved scan
     dpp_scan<3>(r3, lane, 0, false);
     nd = sqrt(readlane_d(r3[0], 63));
@@ -3725,7 +3725,7 @@ struct Small {
     if (!(SOCP_KO & 16)) gemv_G_r<true>(xq, S_, H_, DZ);
 #pragma unroll
     for (int t = 0; t < NS; ++t)
-      if (64 * t + lane < k) zs += zv[t] * sv[t];
+      if (64 * t + lane < k) zs = fma(zv[t], sv[t], zs);  // (explicit: every instantiation sums z's alike, socp_batch_solve_qp's res at P = 0 included)
     if (SOCP_KO & 64) {
       nd = np_ = gap = d2 + p2 + zs;
     } else {

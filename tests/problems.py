@@ -79,16 +79,17 @@ def perturb_G(G, seed):
     return np.where(up, np.nextafter(G, np.inf), np.nextafter(G, -np.inf))
 
 
-def order_floor_traces(oracle, cones, c, A, b, G, h, K, flags, seeds=(1, 2, 3)):
+def order_floor_traces(oracle, cones, c, A, b, G, h, K, flags, seeds=(1, 2, 3), sing=False):
     """The oracle's iterates 1..K in one operation order (flags) and, per
     iterate and vector, the largest relative change under a one-ulp
     perturbation of G over `seeds`: the rounding floor of a comparison with
-    another implementation of the same order.  Returns (iterates[t] = (x, z, s),
+    another implementation of the same order.  sing: the problem's sing flag
+    (H = G'W^-2 G + A'A when set).  Returns (iterates[t] = (x, z, s),
     floor[t] = {"x", "z", "s"})."""
     P = oracle.Params(maxit=K, tol=0.0, flags=flags)
 
     def states(Gx):
-        r = oracle.solve_trace(cones, c, A, b, Gx, h, sing=False, params=P, max_trace=K + 1)
+        r = oracle.solve_trace(cones, c, A, b, Gx, h, sing=bool(sing), params=P, max_trace=K + 1)
         st = list(r["trace"][:r["iters"]]) + [(r["x"], r["y"], r["z"], r["s"])]
         return [(x, z, s) for x, y, z, s in st]
 
@@ -112,18 +113,29 @@ def order_floor_traces(oracle, cones, c, A, b, G, h, K, flags, seeds=(1, 2, 3)):
 FLOOR_FACTOR, FLOOR_ABS = 10.0, 1e-13
 
 
-def trajectory_at_floor(oracle, cfg, d, B, K, flags, solve):
-    """Iterates 1..K of `solve(maxit)` (a batch of B problems of config cfg,
-    generator data d) against the oracle in operation order `flags`, each
-    vector gated by FLOOR_FACTOR * its one-rounding floor + FLOOR_ABS.
-    Returns the (ratio, K, problem, vector, error, floor) rows, worst first."""
+def floor_references(oracle, cfg, d, B, K, flags, sing=False):
+    """order_floor_traces of every problem of a batch (cfg: any object with
+    cones, n, m, k; d: generator data in the flat layout; sing: one flag for
+    the batch)."""
     ref = []
     for p in range(B):
         A = d["A"][p * cfg.m * cfg.n:(p + 1) * cfg.m * cfg.n].reshape(cfg.n, cfg.m).T
         G = d["G"][p * cfg.k * cfg.n:(p + 1) * cfg.k * cfg.n].reshape(cfg.n, cfg.k).T
         ref.append(order_floor_traces(oracle, cfg.cones, d["c"][p * cfg.n:(p + 1) * cfg.n], A,
                                       d["b"][p * cfg.m:(p + 1) * cfg.m], G, d["h"][p * cfg.k:(p + 1) * cfg.k],
-                                      K, flags))
+                                      K, flags, sing=sing))
+    return ref
+
+
+def trajectory_at_floor(oracle, cfg, d, B, K, flags, solve, sing=False, ref=None):
+    """Iterates 1..K of `solve(maxit)` (a batch of B problems of config cfg,
+    generator data d) against the oracle in operation order `flags`, each
+    vector gated by FLOOR_FACTOR * its one-rounding floor + FLOOR_ABS.
+    sing: the batch's sing flag; ref: floor_references of the same arguments,
+    where the caller keeps them.
+    Returns the (ratio, K, problem, vector, error, floor) rows, worst first."""
+    if ref is None:
+        ref = floor_references(oracle, cfg, d, B, K, flags, sing=sing)
     rows = []
     for k_ in range(1, K + 1):
         g = solve(k_)
