@@ -277,7 +277,9 @@ int socp_batch_kkt_solve(socp_ctx* ctx, const socp_dims* dims,
  *                          16x16 tiles, L_PP^-1 on the diagonal; blocked
  *                          kernel: L in place, L_PP^-1 in the diagonal
  *                          blocks), Z = L^-1 A' and S^-1 for S = Z'Z =
- *                          A H^-1 A'; H^-1 itself is never formed.  Where m > 16
+ *                          A H^-1 A' (blocked kernel: the Cholesky factor of
+ *                          S, applied by two triangular solves, here and in
+ *                          socp_batch_kkt_solve); H^-1 itself is never formed.  Where m > 16
  *                          on the register kernel, or with
  *                          SOCP_F_EXPLICIT_INVERSE, it holds Li = H^-1, A Li
  *                          (or Li A') and S^-1, as densesolver.jl:48-51 do;

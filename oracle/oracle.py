@@ -82,6 +82,8 @@ def lib():
         L.or_compute_step.restype = C.c_double
         L.or_compute_scaling.argtypes = cones + [C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
         L.or_compute_scaling.restype = C.c_int
+        L.or_compute_scaling_w.argtypes = cones + [C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
+        L.or_compute_scaling_w.restype = C.c_int
         L.or_scale.argtypes = cones + [_dp, _dp, _dp, _dp, C.c_int]
         L.or_kkt_single.argtypes = (cones + [C.c_int] * 3 + [_dp, _dp, C.c_int] + [_dp] * 6 + [_dp] * 4
                                     + [C.c_void_p, C.c_void_p, C.c_int])
@@ -149,13 +151,17 @@ def compute_step(cones, l, ds, dz):
     return v, dom.value
 
 
-def compute_scaling(cones, s, z):
-    """Returns dict(W, iW, iWiW, l, mu, wbs, status) as scalings.jl:101-110."""
+def compute_scaling(cones, s, z, iwiw=True):
+    """Returns dict(W, iW, iWiW, l, mu, wbs, status) as scalings.jl:101-110.
+    iwiw=False leaves iWiW = iW iW' (k^3 operations) zero."""
     k = len(s)
     W, iW, iWiW = (np.zeros(k * k) for _ in range(3))
     l, wbs = np.zeros(k), np.zeros(k)
     mu = np.zeros(max(len(cones), 1))
-    st = lib().or_compute_scaling(*cone_arrays(cones), k, _f(s), _f(z), W, iW, iWiW, l, mu, wbs)
+    if iwiw:
+        st = lib().or_compute_scaling(*cone_arrays(cones), k, _f(s), _f(z), W, iW, iWiW, l, mu, wbs)
+    else:
+        st = lib().or_compute_scaling_w(*cone_arrays(cones), k, _f(s), _f(z), W, iW, l, mu, wbs)
     return dict(W=W.reshape(k, k, order="F"), iW=iW.reshape(k, k, order="F"),
                 iWiW=iWiW.reshape(k, k, order="F"), l=l, mu=mu, wbs=wbs, status=st)
 

@@ -296,8 +296,9 @@ static void compute_scaling_x(const cones_t* C, scaling_t* S, const double* s, c
     S->l[o] = gamma * tmv1;
   }
   /* iWiW = iW * iW' (scalings.jl:108): dense k^3 GEMM as the reference does
-     (the structured mode applies W^-1 per cone instead and never forms it) */
-  if (structured) return;
+     (the structured mode applies W^-1 per cone instead and never forms it;
+     or_compute_scaling_w passes no iWiW) */
+  if (structured || !S->iWiW) return;
   for (int j = 0; j < k; ++j)
     for (int i = 0; i < k; ++i) {
       double acc = 0.0;
@@ -1223,6 +1224,13 @@ EXPORT int or_compute_scaling(int nc, const int32_t* kind, const int32_t* offs,
   compute_scaling(&C, &S, s, z, &dom);
   free(tmp);
   return dom ? 4 : 0;
+}
+
+/* The same without iWiW = iW iW' (k^3 operations): W, iW, l, mu, wbs. */
+EXPORT int or_compute_scaling_w(int nc, const int32_t* kind, const int32_t* offs,
+                                const int32_t* dim, int k, const double* s, const double* z,
+                                double* W, double* iW, double* l, double* mu, double* wbs) {
+  return or_compute_scaling(nc, kind, offs, dim, k, s, z, W, iW, NULL, l, mu, wbs);
 }
 
 EXPORT void or_scale(int nc, const int32_t* kind, const int32_t* offs, const int32_t* dim,

@@ -2170,6 +2170,18 @@ struct Large : LargeQp<QP> {
   }
 
   // setup_iter (densesolver.jl:41-52): H (+A'A), Li = H^-1, T = Li A', S = A T, S^-1
+  // Whether S = A H^-1 A' is kept as its Cholesky factor and applied by two
+  // triangular solves, not inverted: where m is beyond the sweep's reach, and in
+  // the KKT entries (MODE_KKT, MODE_SETUP, MODE_SOLVEKKT) at every m.  S^-1
+  // applied by symv has no small residual in S cy = m0, and cx = L^-T (u + Z m0)
+  // then carries an error of the size 2^-53 kappa(S) kappa(H)^1/2 where the
+  // solves give 2^-53 kappa(H) (8.5e-2 against 5.6e-8 on a (65, 40, 66) problem
+  // with kappa(S) 7.6e9).  The solver keeps S^-1 for
+  // m <= 512: its trajectories are pinned to that order by the fixtures.
+  __device__ __forceinline__ bool s_factored() const {
+    return CHOL && (L.MPAD > 64 * LARGE_NB_MAX || a.mode != MODE_SOLVE);
+  }
+
   __device__ int factor(bool addAA, bool h_only) {
     LSTAMP(SP_OTHER);
     const bool stg = form_X_fast_ok() && staged_ok();
@@ -2227,8 +2239,8 @@ struct Large : LargeQp<QP> {
     BAR();
     LSTAMP(SP_SCHUR);
     }
-    if (CHOL && L.MPAD > 64 * LARGE_NB_MAX) {
-      // m > 512: S = L_S L_S' in place (the windowed panels of chol_wide); the
+    if (s_factored()) {
+      // S = L_S L_S' in place (m > 512: the windowed panels of chol_wide); the
       // solves apply S^-1 as two triangular solves.  cholesky! of S fails
       // where this does (densesolver.jl:51)
       if (!chol(Sm, L.MPAD)) return ST_CHOL_S;
@@ -2622,7 +2634,7 @@ struct Large : LargeQp<QP> {
     // cx = Li (n0 + A'm0) = L^-T (u + Z m0)
     for (int rep = 0; rep < LREP(16); ++rep) trsv_fwd(Hm, L.NPAD, N0, TN, n);
     mat_mv(Tm, TN, RP, M0);
-    if (L.MPAD > 64 * LARGE_NB_MAX) {  // S = L_S L_S' (factor() factors S beyond the sweep's reach)
+    if (s_factored()) {  // S = L_S L_S' (factor() left the factor, not S^-1)
       trsv_fwd(Sm, L.MPAD, M0, M0, m);
       trsv_bwd(Sm, L.MPAD, M0, RY, m);
     } else {
@@ -2650,6 +2662,16 @@ struct Large : LargeQp<QP> {
     for (int rep = 0; rep < LREP(8); ++rep) gemv_G(RX, -1, K2, K1);
   }
 
+  // the KKT entries' solution of a problem whose scaling or factorisation failed
+  __device__ void kkt_nan(int64_t p) {
+    for (int j = tid; j < n; j += NTH) a.cx[p * n + j] = NAN;
+    for (int i = tid; i < m; i += NTH) a.cy[p * m + i] = NAN;
+    for (int i = tid; i < k; i += NTH) {
+      a.cz[p * k + i] = NAN;
+      a.cs[p * k + i] = NAN;
+    }
+  }
+
   // ------------------------------------------------------------- driver
   // solve_socp (solver.jl:40-153) for problem p: the register kernel's control
   // flow and status rules.
@@ -2666,12 +2688,7 @@ struct Large : LargeQp<QP> {
     if (a.mode == MODE_SOLVEKKT) {  // solve_kkt against the setup_iter record
       const int st0 = (int)Vr[3 * L.KP + 12 * MAXC + 1];
       if (st0) {  // setup_iter failed for this problem: NaN solution, its status
-        for (int j = tid; j < n; j += NTH) a.cx[p * n + j] = NAN;
-        for (int i = tid; i < m; i += NTH) a.cy[p * m + i] = NAN;
-        for (int i = tid; i < k; i += NTH) {
-          a.cz[p * k + i] = NAN;
-          a.cs[p * k + i] = NAN;
-        }
+        kkt_nan(p);
         if (tid == 0) a.status[p] = st0;
         BAR();
         return;
@@ -2741,6 +2758,10 @@ struct Large : LargeQp<QP> {
           }
         }
       }
+      // the fused entry returns what setup_iter + solve_kkt return for a failed
+      // problem (socp.h: bitwise the split calls): its status and a NaN solution,
+      // not what the output buffers held before
+      if (status && a.mode == MODE_KKT) kkt_nan(p);
       if (tid == 0) {
         a.status[p] = status;
         if (a.mode == MODE_SETUP) Vr[3 * L.KP + 12 * MAXC + 1] = (double)status;
