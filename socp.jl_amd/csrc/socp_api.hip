@@ -280,7 +280,7 @@ static const SmallVariant* pick_variant(int n, int m, int k) {
 // The blocked kernel (socp_large.hip): n, m <= 2048.  The problem's vectors live in the 160 KiB LDS of a CU when
 // they fit; otherwise (e.g. k = 1000 at n = 512) in the workgroup's slot of the
 // HBM workspace (*gv: the GV kernels), with only the problem index in LDS.
-static bool large_fits(int n, int m, int k, int nc, size_t* lds_bytes, bool* gv = nullptr, bool xi = false) {
+static bool large_fits(int n, int m, int k, int nc, size_t* lds_bytes, bool* gv = nullptr) {
   // Every LDS / vector offset of the kernel (LargeLayout::o_*, total, LV(int))
   // is a 32-bit int and X = W^-1 G (KP x NPAD) is addressed from int row
   // offsets: bound k before the layout is computed in int, so that neither
@@ -296,7 +296,6 @@ static bool large_fits(int n, int m, int k, int nc, size_t* lds_bytes, bool* gv 
   // n, m: up to 64 LARGE_NB_MAX_CHOL with Cholesky factors of H and S (wide
   // panels in windows, socp_large.hip panel_chol_wide), in both operation
   // orders (SOCP_F_EXPLICIT_INVERSE forms Li and S^-1 from those factors)
-  (void)xi;
   if (L.NPAD > 64 * LARGE_NB_MAX_CHOL || L.MPAD > 64 * LARGE_NB_MAX_CHOL || nc > MAXC) return false;
   size_t lds = (size_t)L.total * sizeof(double);
   const bool g = lds + 64 > 160 * 1024;
@@ -383,7 +382,7 @@ static int launch_small(socp_ctx* ctx, SmallArgs& args, const SmallVariant* v, b
   size_t lds = small_lds_bytes(v->NQ, v->NP, v->MQ);
   if (lds > 160 * 1024) return fail(SOCP_E_UNSUPPORTED, "LDS footprint too large");
   const bool solver = args.mode == MODE_SOLVE;
-  // SOCP_F_EXPLICIT_INVERSE: the sweep variants (m <= 16 shapes; larger m sweep anyway)
+  // SOCP_F_EXPLICIT_INVERSE: the explicit-inverse variants (m <= 16 shapes; larger m form Li anyway)
   const bool xi = (args.flags & SOCP_F_EXPLICIT_INVERSE) != 0 && v->xi_kernel;
   // SOCP_F_DETECT_INFEASIBLE: the solver instantiation with the rule (never with xi: check_detect_flags)
   const bool di = solver && !xi && (args.flags & SOCP_F_DETECT_INFEASIBLE) != 0;
@@ -434,7 +433,7 @@ static int launch_large(socp_ctx* ctx, const SmallArgs& a, double* rec = nullptr
   size_t lds = 0;
   bool gv = false;
   const bool xi = (a.flags & SOCP_F_EXPLICIT_INVERSE) != 0;
-  if (!large_fits(a.n, a.m, a.k, a.nc, &lds, &gv, xi)) return fail(SOCP_E_UNSUPPORTED, kUnsupported);
+  if (!large_fits(a.n, a.m, a.k, a.nc, &lds, &gv)) return fail(SOCP_E_UNSUPPORTED, kUnsupported);
   const bool di = a.mode == MODE_SOLVE && !xi && (a.flags & SOCP_F_DETECT_INFEASIBLE) != 0;
   const void* kern = large_kernel_ptr(xi, gv, di, qp);
   if (!kern) return fail(SOCP_E_UNSUPPORTED, "no compiled kernel for these flags");
@@ -611,7 +610,7 @@ static int batch_solve_impl(socp_ctx* ctx, const socp_dims* dims, const int32_t*
   const bool force_large = (P.flags & SOCP_F_FORCE_LARGE) != 0;
   const SmallVariant* v = (force_large || dims->ncones > NCS) ? nullptr : pick_variant(n, m, k);
   if (qp && v && !v->qp_kernel) v = nullptr;  // no QP instantiation of the shape: the blocked kernel
-  if (!v && !large_fits(n, m, k, dims->ncones, nullptr, nullptr, (P.flags & SOCP_F_EXPLICIT_INVERSE) != 0))
+  if (!v && !large_fits(n, m, k, dims->ncones, nullptr))
     return fail(SOCP_E_UNSUPPORTED, kUnsupported);
   HIPCHK(hipSetDevice(ctx->device));
   const bool dev = (P.flags & SOCP_F_DEVICE_PTRS) != 0;
@@ -736,7 +735,7 @@ extern "C" int socp_batch_kkt_solve(socp_ctx* ctx, const socp_dims* dims, const 
     return fail(SOCP_E_INVALID, "NULL data pointer");
   const bool force_large = (flags & SOCP_F_FORCE_LARGE) != 0;
   const SmallVariant* v = (force_large || dims->ncones > NCS) ? nullptr : pick_variant(n, m, k);
-  if (!v && !large_fits(n, m, k, dims->ncones, nullptr, nullptr, (flags & SOCP_F_EXPLICIT_INVERSE) != 0))
+  if (!v && !large_fits(n, m, k, dims->ncones, nullptr))
     return fail(SOCP_E_UNSUPPORTED, kUnsupported);
   HIPCHK(hipSetDevice(ctx->device));
   const bool dev = (flags & SOCP_F_DEVICE_PTRS) != 0;
@@ -865,7 +864,7 @@ extern "C" int socp_dense_create(socp_ctx* ctx, const socp_dims* dims, const int
   if (B > 0 && (!G || (m > 0 && !A))) return bail(fail(SOCP_E_INVALID, "NULL data pointer"));
   const bool force_large = (flags & SOCP_F_FORCE_LARGE) != 0;
   h->v = (force_large || dims->ncones > NCS) ? nullptr : pick_variant(n, m, k);
-  if (!h->v && !large_fits(n, m, k, dims->ncones, nullptr, nullptr, (flags & SOCP_F_EXPLICIT_INVERSE) != 0))
+  if (!h->v && !large_fits(n, m, k, dims->ncones, nullptr))
     return bail(fail(SOCP_E_UNSUPPORTED, kUnsupported));
   if (hipSetDevice(ctx->device) != hipSuccess) return bail(fail(SOCP_E_HIP, "hipSetDevice"));
   const bool dev = (flags & SOCP_F_DEVICE_PTRS) != 0;

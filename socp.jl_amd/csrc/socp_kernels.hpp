@@ -13,8 +13,8 @@ struct SmallVariant {
   const char* name;
   const void* kkt_kernel;  // socp_small_kernel<NQ,NP,MQ,1>: MODE_KKT / MODE_SETUP / MODE_SOLVEKKT
   const char* kkt_name;
-  // SOCP_F_EXPLICIT_INVERSE (KM 2 / 3): the same two with Li = H^-1 formed by
-  // the sweep; NULL where the shape sweeps anyway (m > 16)
+  // SOCP_F_EXPLICIT_INVERSE (KM 2 / 3): the same two with Li = H^-1 formed
+  // from the Cholesky factor; NULL where the shape forms it anyway (m > 16)
   const void* xi_kernel;
   const char* xi_name;
   const void* xi_kkt_kernel;
@@ -36,7 +36,10 @@ const SmallVariant* small_variants(int* count);
 // ------------------------------------------------------- blocked kernel
 // socp_large.hip: one 512-thread workgroup per problem, the problem's vectors
 // in LDS, its matrices in a per-workgroup slot of an HBM workspace.
-constexpr int LARGE_NB_MAX = 8;  // NPAD, MPAD <= 512: a swept panel row lives in registers
+// NPAD, MPAD <= 512: the bound below which the solver keeps S^-1 (socp_large.hip
+// s_factored; above it S stays factored), and the width of the panel register
+// window (panel_tiles; wider panels go through panel_chol_wide)
+constexpr int LARGE_NB_MAX = 8;
 // NPAD <= 2048 where H is factored (the default, not SOCP_F_EXPLICIT_INVERSE):
 // panels wider than 512 are factored in windows (socp_large.hip panel_chol_wide)
 constexpr int LARGE_NB_MAX_CHOL = 32;
@@ -113,7 +116,7 @@ struct LargeArgs {
   int64_t wstride;  // doubles per workspace slot
   double* rec;      // MODE_SETUP / MODE_SOLVEKKT: per-problem records (B x r_total), else NULL
 };
-// xi: the explicit-inverse build (Li = H^-1 by the sweep, SOCP_F_EXPLICIT_INVERSE);
+// xi: the explicit-inverse build (Li = H^-1 from the Cholesky factor, SOCP_F_EXPLICIT_INVERSE);
 // gv: the problem's vectors in the HBM workspace instead of LDS (shapes whose
 // vectors exceed a CU's 160 KiB of LDS)
 // di: the solver with the infeasibility rule (SOCP_F_DETECT_INFEASIBLE; not with xi)

@@ -7,26 +7,31 @@
 // problem's vectors live in LDS (C4: 126 KiB), its matrices in the workgroup's
 // slot of an HBM workspace, all column-major:
 //   Xw = W^-1 G (KP x NPAD), rebuilt from G at every factorisation;
-//   Hm = H -> -H^-1 (sweep, lower triangle) -> Li = H^-1 (both triangles);
-//   Ap, At = A zero-padded, column- and row-major;  Tm = Li A' (NPAD x MPAD);
-//   Sm = S -> S^-1;  Yp = the sweep's captured pivot rows (64 x max(NPAD, MPAD)).
+//   Hm = H -> its Cholesky factor L (columns of L, and L_PP^-1 in the diagonal
+//     blocks), or with SOCP_F_EXPLICIT_INVERSE -> Li = H^-1 (both triangles);
+//   Ap, At = A zero-padded, column- and row-major;
+//   Tm = Z = L^-1 A', or Li A' (NPAD x MPAD);
+//   Sm = S -> S^-1, or S's Cholesky factor (s_factored);
+//   Yp = panel scratch: the S sweep's pivot rows, the wide panels' saved tiles.
 // Per iteration (solver.jl:105-151) the algebra of the register kernel:
 //   H = X'X (+A'A) as f64-MFMA 64x64 blocks: the reference's iWiW GEMM and
 //     G'*iWiW*G products (scalings.jl:108, densesolver.jl:42-46) structurally;
-//   Li = H^-1 by a blocked symmetric Gauss-Jordan sweep (densesolver.jl:47-48):
-//     each 64-pivot row panel is swept in registers (a thread holds 8 panel
-//     rows x NPAD/64 columns; the pivots are the Cholesky pivots, so the
-//     positive-definiteness test is cholesky!'s), and the rank-64 update of
-//     the other blocks is deferred into one MFMA Gram product per panel;
-//   T = Li A', S = A T and S^-1 by the same sweep (densesolver.jl:49-51);
+//   H = L L' by a left-looking blocked Cholesky factorisation (chol_nb,
+//     densesolver.jl:47): each 64-column panel first takes the Gram updates of
+//     the panels before it (MFMA), then its pivot block is factored by 16x16
+//     tiles (panel_tiles / factor_tile; the positive-definiteness test is
+//     cholesky!'s).  Li is not formed: Z = L^-1 A', S = Z'Z, and Li's products
+//     in the solves are triangular solves.  With SOCP_F_EXPLICIT_INVERSE,
+//     Li = L^-T L^-1 (chol_inverse, :48), T = Li A', S = A T (:49-50);
+//   S^-1 (:51): the solver at m <= 512 forms it by a blocked symmetric
+//     Gauss-Jordan sweep over the same panel kernel (sweep_nb); the plugin
+//     entries and m > 512 keep S's Cholesky factor; the explicit-inverse
+//     kernels invert it from its factor;
 //   the two KKT solves (densesolver.jl:54-90) as mat-vecs over the workspace.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
-#ifndef SOCP_LG_TILE_INPLACE
-#define SOCP_LG_TILE_INPLACE 1  // factor_tile's trailing updates in place (0: copying form, A/B)
-#endif
 #define SOCP_MULTI_WAVE 1  // LANE_IDS / factor_tile: lanes of 8-wavefront workgroups
 #include "socp_kernels.hpp"
 
@@ -40,32 +45,8 @@
 #define SOCP_LREP 0
 #endif
 #define LREP(b) ((SOCP_LREP & (b)) ? 2 : 1)
-#ifndef SOCP_LG_CATCH_SPLIT
-#define SOCP_LG_CATCH_SPLIT 1  // chol_nb: split the last panels' catch-up blocks by 16-column groups
-#endif
-#ifndef SOCP_LG_SYRK_SYNC
-#define SOCP_LG_SYRK_SYNC 128  // form_H: rows of k between workgroup barriers (0: none)
-#endif
-#ifndef SOCP_LG_FX_RS
-#define SOCP_LG_FX_RS 1  // W^-1 G: the 32 cone sums of a pass by one reduce-scatter (0: 32 all-reduces)
-#endif
 #ifndef SOCP_LG_KO
 #define SOCP_LG_KO 0  // timing knock-outs of the W^-1 G phase (tuning builds only; results wrong)
-#endif
-#ifndef SOCP_LG_SYRK_ORDER
-#define SOCP_LG_SYRK_ORDER 1  // form_H with SYRK_SYNC at NPAD = 512: the panel-sharing round order (0: row-major)
-#endif
-#ifndef SOCP_LG_SYRK_UNROLL
-#define SOCP_LG_SYRK_UNROLL 1  // blk_gemm's k loop (16 rows per step)
-#endif
-#ifndef SOCP_LG_GRAM_UNROLL
-#define SOCP_LG_GRAM_UNROLL 1  // gram_blkT's 16-row steps per unrolled round
-#endif
-#ifndef SOCP_LG_CATCH_SPLIT_K
-#define SOCP_LG_CATCH_SPLIT_K 2  // split when at most NW / K blocks are left
-#endif
-#ifndef SOCP_LG_ZU
-#define SOCP_LG_ZU 8  // Z = L^-1 A' update: 4-row k-steps per batch of loads (P0 is a multiple of 64; 16: the same time)
 #endif
 
 namespace socp {
@@ -73,7 +54,6 @@ namespace lg {
 
 constexpr int NW = 8;              // wavefronts per workgroup
 constexpr int NTH = 64 * NW;       // threads per workgroup
-constexpr int NBT = LARGE_NB_MAX;  // 64-column blocks a swept panel row may span
 constexpr int CG = 8;              // columns per wavefront pass in the G' / W^-1 G passes
 constexpr int NOPAD = 1 << 30;     // store_blk: no identity padding
 
@@ -146,16 +126,6 @@ __device__ __forceinline__ double wave_max(double v) {
   return readlane_d(x[0], 63);
 }
 
-#ifndef SOCP_LG_PANEL
-#define SOCP_LG_PANEL 1  // 0: the per-pivot rank-1 sweep of a panel (A/B builds)
-#endif
-#ifndef SOCP_LG_INV_CHOL
-#define SOCP_LG_INV_CHOL 1  // 0: explicit inverses by the Gauss-Jordan sweep (A/B builds)
-#endif
-#ifndef SOCP_LG_CHOL
-#define SOCP_LG_CHOL 1  // 0: Li = H^-1 formed (A/B builds)
-#endif
-
 // C += U'V (NEG = 1: C -= U'V) for C/D-layout 16x16 tiles (socp_small.hpp's
 // tile algebra: lane (g, cl) holds X[g+4r][cl] in register r)
 template <int NEG>
@@ -183,11 +153,10 @@ struct LargeQp<true> {
 };
 template <bool XI, bool GV, bool DI = false, bool QP = false>
 struct Large : LargeQp<QP> {
-  static constexpr bool CHOL = SOCP_LG_CHOL && !XI;
-  // where Li = H^-1 is formed (XI, and every shape of a SOCP_LG_CHOL=0 build):
-  // from the Cholesky factor, Li = L^-T L^-1 (chol_inverse), as
-  // densesolver.jl:47-48 forms it; S^-1 likewise (0: the Gauss-Jordan sweep)
-  static constexpr bool INV_CHOL = SOCP_LG_INV_CHOL && !CHOL;
+  // CHOL: H = L L' kept as its factor, Li's products are triangular solves.
+  // INV_CHOL (XI): Li = H^-1 formed from the Cholesky factor, Li = L^-T L^-1
+  // (chol_inverse), as densesolver.jl:47-48 forms it; S^-1 likewise
+  static constexpr bool CHOL = !XI, INV_CHOL = XI;
   gdbl* gvec = nullptr;  // GV: this workgroup's vector region (workspace slot)
   __device__ __forceinline__ auto& lvref(int i) const {
     if constexpr (GV)
@@ -699,7 +668,8 @@ struct Large : LargeQp<QP> {
   __device__ __forceinline__ void blk_gemm(d4 (&acc)[4][4], gcdbl* P, gcdbl* Q, int ld, int I0,
                                            int J0, int kr, bool same, int qs) {
     const int g = lane >> 4, cl = lane & 15;
-#pragma unroll SOCP_LG_SYRK_UNROLL
+    constexpr int SYRK_UNROLL = 1;  // the k loop (16 rows per step)
+#pragma unroll SYRK_UNROLL
     for (int k0 = 0; k0 < kr; k0 += 16) {
       double av[4][4], bv[4][4];
 #pragma unroll
@@ -755,7 +725,8 @@ struct Large : LargeQp<QP> {
   template <bool LO = false, bool FV = true>
   __device__ __forceinline__ void gram_blkT(d4 (&acc)[4][4], gcdbl* Y, int ld, int I0, int J0, gcdbl* fv) {
     const int g = lane >> 4, cl = lane & 15;
-#pragma unroll SOCP_LG_GRAM_UNROLL
+    constexpr int GRAM_UNROLL = 1;  // 16-row steps per unrolled round
+#pragma unroll GRAM_UNROLL
     for (int k0 = 0; k0 < 64; k0 += 16) {
       double av[4][4], bv[4][4];
 #pragma unroll
@@ -892,10 +863,8 @@ struct Large : LargeQp<QP> {
   // a wavefront takes FX_CG columns at a time and loads them whole (one HBM
   // round trip per pass), reduces every cone's wbar-weighted tail sum from
   // registers, and writes the columns of X.  Otherwise form_X.
-#ifndef SOCP_LG_FX_CG
-#define SOCP_LG_FX_CG 4  // W^-1 G fast path: columns per wavefront pass (2: +2.4 ms at C4, round 5)
-#endif
-  static constexpr int FX_CG = SOCP_LG_FX_CG, FX_NC = 8, FX_R = 10;
+  // FX_CG: columns per wavefront pass (2: +2.4 ms at C4, round 5)
+  static constexpr int FX_CG = 4, FX_NC = 8, FX_R = 10;
   static_assert(FX_CG * FX_NC <= 32, "per-wavefront fx slots: 32 sums, then 32 head values");
   __device__ bool form_X_fast_ok() const { return nc - csoc <= FX_NC && (k + 63) / 64 <= FX_R; }
   // chunked: X in 4-row chunks, chunk-major -- X[i][j] at ((i/4) NPAD + j) 4 + i%4
@@ -970,11 +939,9 @@ struct Large : LargeQp<QP> {
       gcdbl* g0p = Gp + (int64_t)(j0 < nn ? j0 : 0) * kk;
       gdbl* x0 = Xw + (int64_t)j0 * KP;
       load_cols(gv, j0);
-#if SOCP_LG_FX_RS
       double rsv[FX_CG * FX_NC];  // slot u * FX_NC + ci: this lane's partial of del
 #pragma unroll
       for (int q = 0; q < FX_CG * FX_NC; ++q) rsv[q] = 0.0;
-#endif
       // per SOC cone: del = sum over the tail of wbar_i G_ij
 #pragma unroll
       for (int ci = 0; ci < FX_NC; ++ci) {
@@ -990,10 +957,8 @@ struct Large : LargeQp<QP> {
 #pragma unroll
           for (int u = 0; u < FX_CG; ++u) pd[u] = fma(w, gv[u][r], pd[u]);
         }
-#if SOCP_LG_FX_RS
 #pragma unroll
         for (int u = 0; u < FX_CG; ++u) rsv[u * FX_NC + ci] = pd[u];
-#endif
         // the head value G[o][j0 + u] is already in a register (row o of the
         // loaded columns: lane o % 64, slot o / 64): a readlane instead of a
         // global load per column and cone on the wave's critical path
@@ -1008,22 +973,9 @@ struct Large : LargeQp<QP> {
           } else {
             gh = g0p[(int64_t)(u < nl ? u : 0) * kk + o];
           }
-#if SOCP_LG_FX_RS
           if (ln == 0) LV(fx + 32 + u * FX_NC + ci) = gh;
-#else
-#if SOCP_LG_KO & 1  // timing knock-out (tuning builds only; results wrong): no reductions
-          const double del = pd[u];
-#else
-          const double del = wave_sum(pd[u]);
-#endif
-          if (ln == 0) {
-            LV(fx + u * FX_NC + ci) = del;
-            LV(fx + 32 + u * FX_NC + ci) = gh;
-          }
-#endif
         }
       }
-#if SOCP_LG_FX_RS
       // the 32 sums at once by a reduce-scatter over the wavefront: each level
       // halves the values a lane carries and doubles the lanes each covers
       // (lanes +-32 and +-16 by permlane swaps, +-8, +-4, +-2 by DPP, +-1 an
@@ -1031,7 +983,6 @@ struct Large : LargeQp<QP> {
       // instructions instead of 32 wave-wide all-reduces
       fx_reduce_scatter(rsv);
       if ((ln & 1) == 0) LV(fx + (ln >> 1)) = rsv[0];
-#endif
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -1273,45 +1224,31 @@ struct Large : LargeQp<QP> {
   // per block; padding diagonal = 1.
   __device__ __forceinline__ static int syrk_order8(int t) {
     // (I << 3) | J of the t-th block, rounds of eight (form_H)
-#if SOCP_LG_SYRK_ORDER == 2
-    // also balanced over the SIMDs (wavefronts w and w + 4 share one): the
-    // diagonal blocks (10 of 16 tiles) of rounds 1 and 2 on wavefronts 0-3
-    // beside an off-diagonal block each, the last round's four blocks on
-    // wavefronts 0-3 -- every SIMD issues the same MFMAs between barriers
-    // (132 tile-steps per k-step in all, the 528 / 4 minimum; 26 panel reads)
-    constexpr unsigned char tab[36] = {
-        0x00, 0x09, 0x12, 0x1b, 0x08, 0x10, 0x11, 0x18,  // panels 0..3: diagonal, off-diagonal
-        0x24, 0x2d, 0x36, 0x3f, 0x2c, 0x34, 0x35, 0x3c,  // panels 4..7
-        0x20, 0x21, 0x22, 0x23, 0x28, 0x29, 0x2a, 0x2b,  // {4,5} x {0..3}
-        0x30, 0x31, 0x32, 0x33, 0x38, 0x39, 0x3a, 0x3b,  // {6,7} x {0..3}
-        0x19, 0x1a, 0x3d, 0x3e};                         // (3,1) (3,2) (7,5) (7,6)
-#else
     constexpr unsigned char tab[36] = {
         0x00, 0x08, 0x09, 0x10, 0x11, 0x12, 0x18, 0x19,  // panels 0..3
         0x24, 0x2c, 0x2d, 0x34, 0x35, 0x36, 0x3c, 0x3d,  // panels 4..7
         0x20, 0x21, 0x22, 0x23, 0x28, 0x29, 0x2a, 0x2b,  // {4,5} x {0..3}
         0x30, 0x31, 0x32, 0x33, 0x38, 0x39, 0x3a, 0x3b,  // {6,7} x {0..3}
         0x1a, 0x1b, 0x3e, 0x3f};                         // (3,2) (3,3) (7,6) (7,7)
-#endif
     return tab[t];
   }
   __device__ void form_H(bool addAA) {
     const int NB = L.NPAD / 64, nblk = NB * (NB + 1) / 2;
-#if SOCP_LG_SYRK_SYNC > 0
     // The eight wavefronts' blocks of one round share X panels (row-major
     // lower triangle: round 1 reads panels 0..3 for 8 blocks), but a panel
     // row is in L2 only while the wavefronts are within a few k-steps of one
-    // another.  A workgroup barrier every SOCP_LG_SYRK_SYNC rows of k keeps
+    // another.  A workgroup barrier every SYRK_SYNC rows of k keeps
     // them in step, so a round reads each of its panels from HBM once instead
     // of once per block.  Idle wavefronts of the last round keep the count.
     if (!addAA) {
-      constexpr int KB = SOCP_LG_SYRK_SYNC;
+      constexpr int SYRK_SYNC = 128;  // rows of k between workgroup barriers
+      constexpr int KB = SYRK_SYNC;
       const int KP = L.KP;
       for (int r = 0; r < nblk; r += NW) {
         const int t = r + wv;
         int I = 0, J = 0;
         if (t < nblk) {
-          if (SOCP_LG_SYRK_ORDER && NB == 8 && NW == 8) {
+          if (NB == 8 && NW == 8) {
             // rounds over few panels: the 0..3 and 4..7 triangles (4 panels
             // each), {4,5} x {0..3} and {6,7} x {0..3} (6 each), the rest (4):
             // 24 panel reads per SYRK instead of the row-major order's 30
@@ -1344,7 +1281,6 @@ struct Large : LargeQp<QP> {
       BAR();
       return;
     }
-#endif
     for (int t = wv; t < nblk; t += NW) {
       int I, J;
       tri_ij(t, I, J);
@@ -1430,7 +1366,7 @@ struct Large : LargeQp<QP> {
         for (int s_ = 0; s_ < t; ++s_) C = tile_mm<1>(Ys[s_], Ys[s_], C);  // D_tt - sum L_ts L_ts'
         d4 Wt;
         bool ok = true;
-        factor_tile<SOCP_LG_TILE_INPLACE != 0>(C, Wt, ok);
+        factor_tile<true, true>(C, Wt, ok);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
 #pragma unroll
@@ -1571,7 +1507,8 @@ struct Large : LargeQp<QP> {
   template <int nb>
   __device__ bool chol_nb(gdbl* M, int ld) {
     for (int P = 0; P < nb; ++P) {
-      if (P > 0 && SOCP_LG_CATCH_SPLIT && SOCP_LG_CATCH_SPLIT_K * (nb - P) <= NW) {
+      constexpr int CATCH_SPLIT_K = 2;  // split when at most NW / K blocks are left
+      if (P > 0 && CATCH_SPLIT_K * (nb - P) <= NW) {
         // few blocks left: each block's catch-up split into its four 16-column
         // groups, one per wavefront (bitwise the whole-block result)
         for (int it = wv; it < 4 * (nb - P); it += NW) {
@@ -1656,7 +1593,7 @@ struct Large : LargeQp<QP> {
             for (int s_ = 0; s_ < t; ++s_) C = tile_mm<1>(Ys[s_], Ys[s_], C);  // D_tt - sum L_ts L_ts'
             d4 Wt;
             bool ok = true;
-            factor_tile<SOCP_LG_TILE_INPLACE != 0>(C, Wt, ok);
+            factor_tile<true, true>(C, Wt, ok);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
 #pragma unroll
@@ -1788,18 +1725,19 @@ struct Large : LargeQp<QP> {
         d4 acc0, acc1 = zero;
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc0[r] = Ap[(int64_t)(P0 + 16 * ta + g + 4 * r) * MP + 16 * tb + cl];
-        // 4 SOCP_LG_ZU rows per round, their loads issued before the MFMAs (one
+        // 4 ZU rows per round, their loads issued before the MFMAs (one
         // memory round trip per 32 rows instead of per 8); acc0 / acc1 take the
         // same rows in the same order as before
-        for (int y0 = 0; y0 < P0; y0 += 4 * SOCP_LG_ZU) {
-          double a[SOCP_LG_ZU], b[SOCP_LG_ZU];
+        constexpr int ZU = 8;  // 4-row k-steps per batch of loads (P0 is a multiple of 64; 16: the same time)
+        for (int y0 = 0; y0 < P0; y0 += 4 * ZU) {
+          double a[ZU], b[ZU];
 #pragma unroll
-          for (int u = 0; u < SOCP_LG_ZU; ++u) {
+          for (int u = 0; u < ZU; ++u) {
             a[u] = Lm[(int64_t)(y0 + 4 * u + g) * ld + P0 + 16 * ta + cl];
             b[u] = Tm[(int64_t)(y0 + 4 * u + g) * MP + 16 * tb + cl];
           }
 #pragma unroll
-          for (int u = 0; u < SOCP_LG_ZU; u += 2) {
+          for (int u = 0; u < ZU; u += 2) {
             acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[u], acc0, 0, 0, 1);  // -= L Z
             acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u + 1], b[u + 1], acc1, 0, 0, 1);
           }
@@ -1963,23 +1901,15 @@ struct Large : LargeQp<QP> {
 
   // Blocked symmetric Gauss-Jordan sweep of the 64nb x 64nb symmetric matrix
   // whose lower triangle is stored in M (column-major, ld); leaves -M^-1 in the
-  // lower triangle.  Panel P: thread (wave w, lane l) holds panel rows
-  // 64P + w + 8q (q < 8) at columns 64t + l; at step c the owner of row c
-  // publishes it through LDS (the pivot column is the same row by symmetry,
-  // which the update keeps exact: one product per (i,j)/(j,i) pair) and records
-  // it in Yp.  Pivot d = the Schur complement = (Cholesky diagonal)^2, so the
-  // failure test is the one LAPACK potrf applies (d <= 0 or NaN).  The other
-  // blocks get M_IJ -= sum_c rc_c[I]' rc_c[J] / d_c once per panel (MFMA).
+  // lower triangle.  Panel P (64 pivot rows) is swept by panel_tiles, a tile
+  // Cholesky of its pivot block that records the rows Y = L^-1 M_P in Yp; its
+  // pivots are the Cholesky pivots, so the failure test is the one LAPACK potrf
+  // applies (d <= 0 or NaN).  The other blocks get M_IJ -= Y_I' Y_J once per
+  // panel (MFMA).  The solver's S^-1 (m <= 512) is formed this way.
   template <int nb>
   __device__ bool sweep_nb(gdbl* M, int ld) {
-    // members copied to locals: the step loop has a barrier in it, after which
-    // members (this is a stack object once sweep is an out-of-line call) would
-    // be reloaded from scratch
-    const int rr = wv, ln = lane, t0 = tid, o_row = L.o_row, RW = L.RW;
+    const int rr = wv, RW = L.RW;
     for (int P = 0; P < nb; ++P) {
-      const int P0 = 64 * P;
-      gdbl* const Y = Yp + (int64_t)P * 64 * RW;  // this panel's pivot rows
-      gdbl* const rv = Rv + P0;                    // and -1/d of its pivots
       // Catch-up of row block P: its blocks receive the Gram updates of the
       // earlier panels they have not seen (block (t, P), t >= P: panels [0, P);
       // block (P, t), t < P: panels (t, P) -- panel t swept it as part of row t)
@@ -2002,97 +1932,9 @@ struct Large : LargeQp<QP> {
       }
       BAR();
       LSTAMP(NSTAMP + 1 + 0);
-#if SOCP_LG_PANEL
       const bool ok = panel_tiles<nb>(M, ld, P);
       LSTAMP(NSTAMP + 1 + 1);
       if (!ok) return false;
-#else
-      double Z[8][nb];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int x = P0 + rr + 8 * q;
-#pragma unroll
-        for (int t = 0; t < nb; ++t) {
-          const int y = 64 * t + ln;  // element (x, y) from the lower triangle
-          Z[q][t] = M[(y <= x) ? (int64_t)y * ld + x : (int64_t)x * ld + y];
-        }
-      }
-      bool ok = true;
-      for (int c = 0; c < 64; ++c) {
-        const int buf = o_row + (c & 1) * RW;
-        if (rr == (c & 7)) {
-          const int qc = c >> 3;
-#pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            if (q == qc) {
-#pragma unroll
-              for (int t = 0; t < nb; ++t) {
-                LV(buf + 64 * t + ln) = Z[q][t];
-                Y[(int64_t)c * RW + 64 * t + ln] = Z[q][t];  // coalesced row store
-              }
-            }
-          }
-        }
-        LDS_BAR();  // the pivot row's Yp / rv stores drain by the panel's BAR()
-        const double d = LV(buf + P0 + c);
-        ok = ok && (d > 0.0);
-        const double r = 1.0 / d;
-        if (t0 == 0) rv[c] = -r;
-        double rowv[nb], colv[8];
-#pragma unroll
-        for (int t = 0; t < nb; ++t) rowv[t] = LV(buf + 64 * t + ln);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) colv[q] = LV(buf + P0 + rr + 8 * q);
-        // rank-1 update of every element as (col_i sqrt(r)) (row_j sqrt(r)): one
-        // FMA per element, and (i,j), (j,i) multiply the same two numbers, so the
-        // diagonal block stays exactly symmetric (r = 1/d > 0 whenever ok holds);
-        // then the pivot column (block P, lane c: a select) and the pivot row
-        // (one register row of one wavefront)
-        const double sr = sqrt(r);
-        double rsq[nb], csq[8];
-#pragma unroll
-        for (int t = 0; t < nb; ++t) rsq[t] = rowv[t] * sr;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) csq[q] = colv[q] * sr;
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-#pragma unroll
-          for (int t = 0; t < nb; ++t) Z[q][t] = fma(-csq[q], rsq[t], Z[q][t]);
-        const bool lc = ln == c;
-#pragma unroll
-        for (int t = 0; t < nb; ++t)
-          if (t == P) {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) Z[q][t] = lc ? colv[q] * r : Z[q][t];
-          }
-        if (rr == (c & 7)) {
-          const int qc = c >> 3;
-#pragma unroll
-          for (int q = 0; q < 8; ++q)
-            if (q == qc) {
-#pragma unroll
-              for (int t = 0; t < nb; ++t) Z[q][t] = (t == P && lc) ? -r : rowv[t] * r;
-            }
-        }
-      }
-      BAR();  // Yp and the pivot reciprocals complete
-      LSTAMP(NSTAMP + 1 + 1);
-      if (!ok) return false;
-      {
-        // addresses recomputed from a fresh lane id: reusing the load's would
-        // keep 64 of them live (spilled) across the step loop
-        const int lf = lane_fresh();
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const int x = P0 + rr + 8 * q;
-#pragma unroll
-          for (int t = 0; t < nb; ++t) {
-            const int y = 64 * t + lf;
-            M[(y <= x) ? (int64_t)y * ld + x : (int64_t)x * ld + y] = Z[q][t];
-          }
-        }
-      }
-#endif
       BAR();  // panel P written back before the next catch-up reads its neighbours
       LSTAMP(NSTAMP + 1 + 2);
     }
@@ -2201,24 +2043,18 @@ struct Large : LargeQp<QP> {
     if constexpr (CHOL) {
     if (!chol(Hm, L.NPAD)) return ST_CHOL_H;
     if (h_only) return 0;
-    LSTAMP(SP_SWEEP_H);
+    LSTAMP(SP_FACTOR_H);
     for (int rep = 0; rep < LREP(32); ++rep) {
       chol_fwd_multi(Hm, L.NPAD);
       form_S_gram();
     }
     LSTAMP(SP_SCHUR);
     } else {
-    if constexpr (INV_CHOL) {
-      if (!chol(Hm, L.NPAD)) return ST_CHOL_H;
-      if (h_only) return 0;
-      chol_inverse(Hm, L.NPAD);
-    } else {
-      if (!sweep(Hm, L.NPAD)) return ST_CHOL_H;
-      if (h_only) return 0;
-      finalize_sym(Hm, L.NPAD);
-    }
+    if (!chol(Hm, L.NPAD)) return ST_CHOL_H;
+    if (h_only) return 0;
+    chol_inverse(Hm, L.NPAD);
     LSTAMP(NSTAMP + 1 + 4);
-    LSTAMP(SP_SWEEP_H);
+    LSTAMP(SP_FACTOR_H);
     const int NB = L.NPAD / 64, MB = L.MPAD / 64;
     for (int t = wv; t < NB * MB; t += NW) {
       const int I = t / MB, J = t - I * MB;
@@ -2251,6 +2087,7 @@ struct Large : LargeQp<QP> {
       if (!chol(Sm, L.MPAD)) return ST_CHOL_S;
       chol_inverse(Sm, L.MPAD);
     } else {
+      // the solver's S^-1 at m <= 512 (s_factored above): the Gauss-Jordan sweep
       if (!sweep(Sm, L.MPAD)) return ST_CHOL_S;
       finalize_sym(Sm, L.MPAD);
     }
@@ -2264,12 +2101,9 @@ struct Large : LargeQp<QP> {
   // load of the pass in flight at once (GT_R x CG per lane) -- instead of one
   // 64-row step of the CG columns per memory round trip.
   static constexpr int GT_R = 10;
-#ifndef SOCP_LG_GT_FAST
-#define SOCP_LG_GT_FAST 1
-#endif
   __device__ void gemv_Gt(int vin, int vout, int vadd) {
     LSTAMP(SP_SOLVE);
-    if (SOCP_LG_GT_FAST && k <= 64 * GT_R) {
+    if (k <= 64 * GT_R) {
       double vr[GT_R];
 #pragma unroll
       for (int r = 0; r < GT_R; ++r) vr[r] = (lane + 64 * r < k) ? LV(vin + lane + 64 * r) : 0.0;
@@ -2332,7 +2166,7 @@ struct Large : LargeQp<QP> {
   static constexpr int CGM = 4;
   __device__ bool gemv_GtG(int zin, int vout, int xin, int add, int sub, int gout) {
     const int KP = L.KP;
-    if (!SOCP_LG_GT_FAST || k > 64 * GT_R || L.o_kvd != 0 || 8 * KP > L.o_part + 8 * L.MPAD) return false;
+    if (k > 64 * GT_R || L.o_kvd != 0 || 8 * KP > L.o_part + 8 * L.MPAD) return false;
     LSTAMP(SP_SOLVE);
     double vr[GT_R], pr[GT_R];
 #pragma unroll

@@ -12,10 +12,11 @@
 //   - H = X'X with X = W^-1 G generated in registers and contracted by f64
 //     MFMA: the reference's iWiW GEMM, G'*iWiW and *G (scalings.jl:108,
 //     densesolver.jl:42-43) done structurally; +A'A if sing (:44-46);
-//   - the explicit inverse Li = H^-1 (densesolver.jl:47-48) by an in-register
-//     symmetric Gauss-Jordan sweep whose pivots are the Cholesky pivots, so
-//     positive-definiteness fails exactly where cholesky! would;
-//   - ALi' = Li A' and S = A Li A' on MFMA, S^-1 by the same sweep (:49-51);
+//   - H = L L' by an in-register blocked Cholesky factorisation on 16x16
+//     tiles (factor_tile), failing where cholesky! would.  m <= 16: Z = L^-1 A'
+//     and S = Z'Z, Li never formed (triangular solves).  Otherwise the explicit
+//     inverse Li = L^-T L^-1 (densesolver.jl:47-48), ALi' = Li A' and
+//     S = A Li A' on MFMA, S^-1 the same way (:49-51);
 //   - two KKT solves (densesolver.jl:54-90) and the step/update.
 // LDS (<40 KiB per wave at n=64) holds only vectors, A and broadcast scratch,
 // so four one-wave blocks (one per SIMD) share a CU.
@@ -199,9 +200,6 @@ enum : int {
   O_FIXED = O_STAMPS + SOCP_NSTAMP_SLOTS  // then (Shape): rcode[KP], 17 k-vectors KS apart, ...
 };
 constexpr int NKV = 17;
-#ifndef SOCP_SYRK_UBT
-#define SOCP_SYRK_UBT 1  // the SYRK's U-row addresses from a launch-wide table (0: from the codes)
-#endif
 // per-cone constants (SOC cones), recomputed by every scaling:
 //   MU = mu, IMU = 1/mu, WB0 = wbar_0, I1 = 1/(1+wbar_0), W2 = |wbar_1|^2,
 //   L0 = lambda_0, AA = lambda_0^2 - |lambda_1|^2 (iprod!'s `a`, vectors.jl:105),
@@ -227,24 +225,33 @@ __host__ __device__ constexpr int small_lda(int NQ, int NP) {
   return (NQ * NP > 24 && NQ > 1) ? 16 * NQ + 2 : 16 * NQ + 1;  // (16 NQ + 2) / 2 is odd
 }
 
-template <int NQ, int NP, int MQ>
-struct Shape {
+// The LDS layout of one shape, in doubles from the wave's base: the one source
+// of Shape's offsets, small_lds_bytes and small_rec_doubles.
+struct SmallLayout {
+  int NPAD, KP, MPAD, LDA, KS;
+  bool AL_LDS, TB_ALIAS, UBT;
+  int O_RC, O_KV, O_A, O_NV, O_MV, UAL, O_U, O_TB, O_UBT, TOTAL;
+};
+__host__ __device__ constexpr SmallLayout small_layout(int NQ, int NP, int MQ) {
+  SmallLayout L{};
   // LDA (row stride of A and of Z' / A Li in LDS): NPAD + 1 on the two-wave
   // shapes (their LDS is tight); on the others NPAD + 2 = 2 x odd, where the
   // A x / Z't reads of a half-wave (lanes cl, g in {0, 1}: cl LDA + g doubles)
   // hit 32 distinct bank pairs, instead of two lanes per pair at NPAD + 1
-  static constexpr int NPAD = 16 * NQ, KP = 4 * NP, MPAD = 16 * MQ,
-                       LDA = small_lda(NQ, NP);
+  L.NPAD = 16 * NQ;
+  L.KP = 4 * NP;
+  L.MPAD = 16 * MQ;
+  L.LDA = small_lda(NQ, NP);
   // k-vector stride KP: lanes read slot 1 / padding elements i >= KP
   // unconditionally and mask the values by their type code (3 = pad), so those
   // reads may alias the next vector (the last one reads into the A block); every
   // write is guarded by i < k or the code, and rows [k, KP) stay zero.
-  static constexpr int KS = KP;
-  static constexpr int O_RC = O_FIXED;       // rcode[KP]: cone*4 + type (0 POC, 1 SOC head, 2 SOC tail, 3 pad)
-  static constexpr int O_KV = O_RC + KP;     // 17 k-vectors, KS apart
-  static constexpr int O_A = O_KV + NKV * KS;
-  static constexpr int O_NV = O_A + MPAD * LDA;    // n-vectors: c x rd rx n0 tn
-  static constexpr int O_MV = O_NV + 6 * NPAD;     // m-vectors: b y rp ry m0 tm
+  L.KS = L.KP;
+  L.O_RC = O_FIXED;            // rcode[KP]: cone*4 + type (0 POC, 1 SOC head, 2 SOC tail, 3 pad)
+  L.O_KV = L.O_RC + L.KP;      // 17 k-vectors, KS apart
+  L.O_A = L.O_KV + NKV * L.KS;
+  L.O_NV = L.O_A + L.MPAD * L.LDA;  // n-vectors: c x rd rx n0 tn
+  L.O_MV = L.O_NV + 6 * L.NPAD;     // m-vectors: b y rp ry m0 tm
   // U[NCS][NPAD] (the SYRK's cone rows) and, for m <= 16, A Li (MPAD x LDA,
   // from the Schur step to the solves): their lifetimes do not overlap.
   // Z' / A Li is written by factor() after form_H and last read by the
@@ -254,19 +261,28 @@ struct Shape {
   // Nothing between the residuals and form_H touches the region (the exit
   // tests and infeas_check read k-, n- and m-vectors only), on the Cholesky,
   // the explicit-inverse and the detecting solvers alike.
-  static constexpr bool AL_LDS = MQ == 1;
-  static constexpr int UAL = (AL_LDS && MPAD * LDA > NCS * NPAD) ? MPAD * LDA : NCS * NPAD;
-  static constexpr int O_U = O_MV + 6 * MPAD;
-  static constexpr int O_AL = O_U;
+  L.AL_LDS = MQ == 1;
+  L.UAL = (L.AL_LDS && L.MPAD * L.LDA > NCS * L.NPAD) ? L.MPAD * L.LDA : NCS * L.NPAD;
+  L.O_U = L.O_MV + 6 * L.MPAD;
   // tile transpose [16][17]: only factor() uses it; on the Cholesky shapes
   // (AL_LDS) in the k-vectors dead during a factorisation when they hold it
-  static constexpr bool TB_ALIAS = AL_LDS && NKV_DEAD * KS >= 16 * 17;
-  static constexpr int O_TB = TB_ALIAS ? O_KV + KV_RZ * KS : O_U + UAL;
+  L.TB_ALIAS = L.AL_LDS && NKV_DEAD * L.KS >= 16 * 17;
+  L.O_TB = L.TB_ALIAS ? L.O_KV + KV_RZ * L.KS : L.O_U + L.UAL;
   // the SYRK's U-row table (int32 per k-row) where the LDS allows (not the
   // two-wave shapes, whose LDS is tight)
-  static constexpr bool UBT = SOCP_SYRK_UBT && NQ * NP > 24 && NQ > 1;
-  static constexpr int O_UBT = O_U + UAL + (TB_ALIAS ? 0 : 16 * 17);
-  static constexpr int TOTAL = O_UBT + (UBT ? (KP + 1) / 2 : 0);
+  L.UBT = NQ * NP > 24 && NQ > 1;
+  L.O_UBT = L.O_U + L.UAL + (L.TB_ALIAS ? 0 : 16 * 17);
+  L.TOTAL = L.O_UBT + (L.UBT ? (L.KP + 1) / 2 : 0);
+  return L;
+}
+
+template <int NQ, int NP, int MQ>
+struct Shape {
+  static constexpr SmallLayout L = small_layout(NQ, NP, MQ);
+  static constexpr int NPAD = L.NPAD, KP = L.KP, MPAD = L.MPAD, LDA = L.LDA, KS = L.KS;
+  static constexpr int O_RC = L.O_RC, O_KV = L.O_KV, O_A = L.O_A, O_NV = L.O_NV, O_MV = L.O_MV;
+  static constexpr bool AL_LDS = L.AL_LDS, TB_ALIAS = L.TB_ALIAS, UBT = L.UBT;
+  static constexpr int UAL = L.UAL, O_U = L.O_U, O_AL = L.O_U, O_TB = L.O_TB, O_UBT = L.O_UBT, TOTAL = L.TOTAL;
   static constexpr int nv(int id) { return O_NV + id * NPAD; }
   static constexpr int mv(int id) { return O_MV + id * MPAD; }
 };
@@ -274,32 +290,27 @@ enum : int { NV_C, NV_X, NV_RD, NV_RX, NV_N0, NV_TN };
 enum : int { MV_B, MV_Y, MV_RP, MV_RY, MV_M0, MV_TM };
 
 // doubles of one factor record of the register kernel: the H^-1 and S^-1
-// tiles in lane order, LAM WB CA CBV IL, the per-cone constants, the sing flag
-inline int64_t small_rec_doubles(int NQ, int NP, int MQ) {
+// tiles in lane order, LAM WB CA CBV IL, the per-cone constants, the sing flag,
+// and on the AL_LDS shapes the A Li block kept in LDS
+constexpr int64_t small_rec_doubles(int NQ, int NP, int MQ) {
+  const SmallLayout L = small_layout(NQ, NP, MQ);
   const int64_t NT = NQ * (NQ + 1) / 2, MT = MQ * (MQ + 1) / 2;
-  const int64_t al = MQ == 1 ? (int64_t)16 * small_lda(NQ, NP) : 0;  // A Li kept in LDS (Shape::AL_LDS)
-  return (NT + MT) * 256 + 5 * (int64_t)(4 * NP) + 20 * NCS + al + 8;
+  const int64_t al = L.AL_LDS ? (int64_t)L.MPAD * L.LDA : 0;
+  return (NT + MT) * 256 + 5 * (int64_t)L.KP + 20 * NCS + al + 8;
 }
 
-inline size_t small_lds_bytes(int NQ, int NP, int MQ) {
-  int NPAD = 16 * NQ, MPAD = 16 * MQ, LDA = small_lda(NQ, NP);
-  int KS = 4 * NP;  // Shape::KS
-  int ual = (MQ == 1 && MPAD * LDA > NCS * NPAD) ? MPAD * LDA : NCS * NPAD;  // Shape::UAL
-  const bool tb_alias = MQ == 1 && NKV_DEAD * KS >= 16 * 17;                // Shape::TB_ALIAS
-  const bool ubt = SOCP_SYRK_UBT && NQ * NP > 24 && NQ > 1;                   // Shape::UBT
-  int total = O_FIXED + KS + NKV * KS + MPAD * LDA + 6 * NPAD + 6 * MPAD + ual + (tb_alias ? 0 : 16 * 17) +
-              (ubt ? (KS + 1) / 2 : 0);
 #ifndef SOCP_DEV_LDS_PAD
 #define SOCP_DEV_LDS_PAD 0  // probe builds only: extra LDS bytes per wave to cap the waves per CU
 #endif
-  return (size_t)total * sizeof(double) + SOCP_DEV_LDS_PAD;
+inline size_t small_lds_bytes(int NQ, int NP, int MQ) {
+  return (size_t)small_layout(NQ, NP, MQ).TOTAL * sizeof(double) + SOCP_DEV_LDS_PAD;
 }
 
 // Diagnostic phase timing (separate build, -DSOCP_DIAG): per-phase s_memtime
 // deltas accumulated per problem and added to a global table by lane 0.
 #ifdef SOCP_DIAG
 #define NSTAMP 12
-#define NSUBSTAMP 11  // sub-phases (0-3 the H sweep, 4-10 solve / cone-op parts), slots NSTAMP+1 ..
+#define NSUBSTAMP 11  // sub-phases (0-3 the H factorisation, 4-10 solve / cone-op parts), slots NSTAMP+1 ..
 // Totals live in LDS (lane 0 read-modify-writes them), so the stamps cost no
 // registers beyond the last timestamp; they are flushed once per wave.
 #define STAMP_DECL uint64_t st_last = 0;
@@ -316,7 +327,7 @@ inline size_t small_lds_bytes(int NQ, int NP, int MQ) {
 #define STAMP_SUB(i) do {} while (0)
 #define STAMP_X(i) do {} while (0)
 #endif
-enum { SP_LOAD, SP_SCALING, SP_RESID, SP_U, SP_SYRK, SP_SWEEP_H, SP_SCHUR, SP_SOLVE, SP_STEP, SP_VOP,
+enum { SP_LOAD, SP_SCALING, SP_RESID, SP_U, SP_SYRK, SP_FACTOR_H, SP_SCHUR, SP_SOLVE, SP_STEP, SP_VOP,
        SP_STORE, SP_OTHER };
 
 // Static-analysis build (-DSOCP_MARK, tools/isa_phases.py): region markers as
@@ -457,17 +468,12 @@ __device__ __forceinline__ double dpp(double v) {
   const int h2 = __builtin_amdgcn_update_dpp(0, hi, CTRL, RM, 0xF, false);
   return __hiloint2double(h2, l2);
 }
-#ifndef SOCP_DPP_B64
-#define SOCP_DPP_B64 1  // 0: row_newbcast of a double as two 32-bit moves too (A/B builds)
-#endif
 // DPP move whose pattern writes every lane (row_newbcast): no old value needed.
 // row_newbcast:N (0x150 + N) of a double is one v_mov_b64_dpp; every other
 // control has no 64-bit form and moves the two halves.
 template <int CTRL>
 __device__ __forceinline__ double dpp_all(double v) {
-#if SOCP_DPP_B64
   if constexpr (CTRL >= 0x150 && CTRL <= 0x15F) return __builtin_amdgcn_mov_dpp(v, CTRL, 0xF, 0xF, false);
-#endif
   const int l2 = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, false);
   const int h2 = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, false);
   return __hiloint2double(h2, l2);
@@ -581,7 +587,7 @@ __device__ __forceinline__ double row_partner(double v) {
 }
 
 // Wave-uniform copies.  LLVM's divergence analysis treats every LDS or global
-// load as divergent; a branch on such a value (the sweep's pivot test, the
+// load as divergent; a branch on such a value (a pivot test, the
 // per-problem `sing` flag, the phase number) is then compiled as exec-masked
 // straight-line code: every arm runs and the live ranges of all arms merge.
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -733,7 +739,7 @@ enum : int {
 enum : int { RET_INIT, RET_KKT, RET_AFFINE, RET_COMBINED };
 
 // ---------------------------------------- 16x16 tile kernels (shared by the
-// register kernel's H^-1 sweep and the blocked kernel's panel factorisation)
+// register kernel's and the blocked kernel's factorisations)
 
 // Broadcast across the four 16-lane rows: every lane gets x from the lane of
 // row R with the same column index (gfx950 v_permlane32_swap / 16_swap).
@@ -783,90 +789,30 @@ __device__ __forceinline__ double sqrt_nr(double d) {
   const double r = d * rsqrt_nr(d);
   return (d == 0.0 || d == INFINITY) ? d : r;
 }
-// the tile factorisation's pivots: SOCP_TILE_NEWTON Newton steps (1: a
-// shorter dependency chain, within a few ulp)
-#ifndef SOCP_TILE_NEWTON
-#define SOCP_TILE_NEWTON 1
-#endif
+// the tile factorisation's pivots: one Newton step (a shorter dependency
+// chain, within a few ulp)
 __device__ __forceinline__ double rsqrt_tile(double d) {
-#if SOCP_TILE_NEWTON == 1
   const double y = __builtin_amdgcn_rsq(d);
   const double e = fma(-(0.5 * d) * y, y, 0.5);
   return fma(y, e, y);
-#else
-  return rsqrt_nr(d);
-#endif
 }
 
-#ifndef SOCP_TILE_FACTOR
-#define SOCP_TILE_FACTOR 2  // 2: pivot blocks in lanes; 1: in wave-uniform values; 0: per pivot (A/B builds)
-#endif
-#ifndef SOCP_TRANSPOSE_MFMA
-#define SOCP_TRANSPOSE_MFMA 0
-#endif
-#ifndef SOCP_U_LANECONES
-#define SOCP_U_LANECONES 1  // compute_U takes the cone descriptors from the cone lanes (0: from the kernel args)
-#endif
-#ifndef SOCP_FUSE_U
-#define SOCP_FUSE_U 1  // the residuals' G x pass can form U (SmallArgs::fuse_u); 0: compute_U() always (A/B builds)
-#endif
-#ifndef SOCP_TILE_OKDIAG
-#define SOCP_TILE_OKDIAG 1  // the pivot test once per tile, on the diagonal of W (0: per pivot)
-#endif
-#ifndef SOCP_S_TILE
-#define SOCP_S_TILE 1  // m <= 16 Cholesky shapes: S^-1 = W'W from one factor_tile (0: Gauss-Jordan sweep)
-#endif
-#ifndef SOCP_TILE_INPLACE
-#define SOCP_TILE_INPLACE 1  // 0: copy back only registers > B (A/B builds)
-#endif
-#if SOCP_TILE_FACTOR == 0
-// Pivot J of row block B of the tile factorisation: v = register B of the
-// (updated) D tile, w = register B of the eliminated identity.  Row J of
-// the block (lanes of row group J) is scaled by 1/sqrt(d) and becomes row
-// 4B+J of L' (R) and of W; the rows below it in the block take the rank-1
-// update.  Rows above it (finished) take garbage, never read again.
-template <int B, int J>
-__device__ __forceinline__ void tile_pivot(double& v, double& w, double& R, double& Wb, bool& ok) {
-  if constexpr (J < 4) {
-    LANE_IDS();
-    const double d = readlane_d(v, 16 * J + 4 * B + J);
-    ok = ok && (d > 0.0);  // NaN fails too: potrf's test
-    const double rs = rsqrt_nr(d);
-    const double vj = row_bcast<J>(v) * rs;
-    const double wj = row_bcast<J>(w) * rs;
-    const double l = dpp_all<0x150 + 4 * B + J>(v) * rs;  // D[4B+g][4B+J] / sqrt(d)
-    v = fma(-l, vj, v);
-    w = fma(-l, wj, w);
-    R = (g == J) ? vj : R;
-    Wb = (g == J) ? wj : Wb;
-    tile_pivot<B, J + 1>(v, w, R, Wb, ok);
-  }
-}
-#endif
 // Row blocks B.. of W = L^-1 for D = L L' (right-looking, 4 rows at a time;
 // the rank-4 trailing update of the D and identity tiles is one MFMA each).
 // Every lane forms the block's rows of R = L' and of W by forward
 // substitution from the broadcast block rows; the 4x4 diagonal block (its
 // upper triangle, as potrf('U') reads it) is read out of those rows by in-row
-// broadcasts (SOCP_TILE_FACTOR 1: factored beforehand in wave-uniform values,
-// the same operations on the same values).
+// broadcasts (!LANES: factored beforehand in wave-uniform values, the same
+// operations on the same values).
 struct NoHook {
   template <int B>
   __device__ __forceinline__ void run() const {}
 };
-template <int B, bool INPL = (SOCP_TILE_INPLACE != 0), bool LANES = (SOCP_TILE_FACTOR == 2), class H = NoHook>
+template <int B, bool INPL, bool LANES, class H = NoHook>
 __device__ __forceinline__ void tile_block(d4& Dt, d4& It, d4& W, bool& ok, const H& hook = H()) {
   if constexpr (B < 4) {
     LANE_IDS();
     double R, Wb;
-#if SOCP_TILE_FACTOR == 0
-    {
-      double v = Dt[B], w = It[B];
-      R = 0.0;
-      Wb = 0.0;
-      tile_pivot<B, 0>(v, w, R, Wb, ok);
-    }
-#else
     if constexpr (LANES) {
       // V[i], X[i]: rows 4B+i of the D and identity tiles in every row group.
       // Row R_i of L' holds the pivot block's own entries at columns 4B..4B+3
@@ -891,12 +837,6 @@ __device__ __forceinline__ void tile_block(d4& Dt, d4& It, d4& W, bool& ok, cons
                    Y3 = fma(-r23, W2, fma(-r13, W1, fma(-r03, W0, X[3])));
       const double rs3 = rsqrt_tile(dpp_all<0x150 + 4 * B + 3>(T3));
       const double R3 = T3 * rs3, W3 = Y3 * rs3;
-#if !SOCP_TILE_OKDIAG
-      {
-        const double dv = g == 0 ? V[0] : (g == 1 ? T1 : (g == 2 ? T2 : T3));
-        ok = ok && __all(cl != 4 * B + g || dv > 0.0);  // NaN fails too
-      }
-#endif
       R = g == 0 ? R0 : (g == 1 ? R1 : (g == 2 ? R2 : R3));
       Wb = g == 0 ? W0 : (g == 1 ? W1 : (g == 2 ? W2 : W3));
     } else {
@@ -918,9 +858,6 @@ __device__ __forceinline__ void tile_block(d4& Dt, d4& It, d4& W, bool& ok, cons
       const double r23 = fma(-r12, r13, fma(-r02, r03, a23)) * rs2;
       const double s33 = fma(-r23, r23, fma(-r13, r13, fma(-r03, r03, a33)));
       const double rs3 = rsqrt_tile(s33);
-#if !SOCP_TILE_OKDIAG
-      ok = ok && (a00 > 0.0) && (s11 > 0.0) && (s22 > 0.0) && (s33 > 0.0);  // NaN fails too
-#endif
       double V[4], X[4];
       row_bcast4(v, V);
       row_bcast4(w, X);
@@ -935,7 +872,6 @@ __device__ __forceinline__ void tile_block(d4& Dt, d4& It, d4& W, bool& ok, cons
       R = g == 0 ? R0 : (g == 1 ? R1 : (g == 2 ? R2 : R3));
       Wb = g == 0 ? W0 : (g == 1 ? W1 : (g == 2 ? W2 : W3));
     }
-#endif
     hook.template run<B>();  // independent MFMA work interleaved with the chain
     W[B] = Wb;
     if constexpr (B < 3 && INPL) {
@@ -959,9 +895,9 @@ __device__ __forceinline__ void tile_block(d4& Dt, d4& It, d4& W, bool& ok, cons
 // cycles vs 3,406 on one wave, profiles/r03_probe_tile.log); the copying form
 // keeps fewer registers live, which the smallest register kernels need to stay
 // at two waves per SIMD.
-// LANES: the pivot blocks in lanes (SOCP_TILE_FACTOR 2) or in wave-uniform
-// values; the same operations on the same values, so the same bits.
-template <bool INPL = (SOCP_TILE_INPLACE != 0), bool LANES = (SOCP_TILE_FACTOR == 2), class H = NoHook>
+// LANES: the pivot blocks in lanes or in wave-uniform values; the same
+// operations on the same values, so the same bits.
+template <bool INPL, bool LANES, class H = NoHook>
 __device__ __forceinline__ void factor_tile(d4 Dt, d4& W, bool& ok, const H& hook = H()) {
   MARK_BEGIN("factor_tile");
   LANE_IDS();
@@ -970,7 +906,6 @@ __device__ __forceinline__ void factor_tile(d4 Dt, d4& W, bool& ok, const H& hoo
   for (int r = 0; r < 4; ++r) It[r] = (g + 4 * r == cl) ? 1.0 : 0.0;
   W = It;
   tile_block<0, INPL, LANES>(Dt, It, W, ok, hook);
-#if SOCP_TILE_OKDIAG
   // potrf's test once per tile: the diagonal of W = L^-1 holds the pivots'
   // 1/sqrt, which is finite and > 0 exactly when every pivot is > 0 (a pivot
   // <= 0 or NaN makes rsqrt_tile NaN; a NaN anywhere reaches every later pivot)
@@ -978,7 +913,6 @@ __device__ __forceinline__ void factor_tile(d4 Dt, d4& W, bool& ok, const H& hoo
 #pragma unroll
   for (int r = 0; r < 4; ++r) dg = dg && (g + 4 * r != cl || W[r] > 0.0);
   ok = ok && __all(dg);
-#endif
 }
 
 
@@ -1010,12 +944,12 @@ struct Small {
   // in-place tile updates (factor_tile) except where G is small enough for two
   // waves per SIMD: C1's <2, 12, 1> takes 209 + 48 registers with them, 208 + 48
   // without
-  static constexpr bool TILE_INPL = SOCP_TILE_INPLACE != 0 && NQ * NP > 24;
-  // the tile's pivot blocks in lanes (SOCP_TILE_FACTOR 2) on the m <= 16
+  static constexpr bool TILE_INPL = NQ * NP > 24;
+  // the tile's pivot blocks in lanes on the m <= 16
   // shapes.  The m > 16 shapes keep the wave-uniform form: with the lane form
   // <2, 4, 2> takes 247 registers instead of 231 and falls to one wave per
   // SIMD, and three more NQ = 4 objects trip the compiler's AGPR-rewrite pass
-  static constexpr bool TILE_LANES = SOCP_TILE_FACTOR == 2 && MQ == 1;
+  static constexpr bool TILE_LANES = MQ == 1;
   // the solves' per-cone constants read ahead of the cone reductions (their
   // latency under the DPP chains) where registers allow: not in the kernels
   // that keep two waves per SIMD (C1's <2, 12, 1> would take 217 + 48; every
@@ -1047,29 +981,12 @@ struct Small {
   AD G[NP][NQ];  // AGPR-resident
   d4 T[NT];
   d4 Sv[MT];
-#ifndef SOCP_KEEP_AL
-#define SOCP_KEEP_AL 0
-#endif
-  // A Li (m x n) as C/D tiles AL[tq][ti] = (A Li)[16tq.., 16ti..]: kept from
-  // the Schur step for the solves' cx = Li n0 + (A Li)' m0 (shapes with at
-  // most 4 such tiles; larger ones take A'm0 and a second Li product)
-  static constexpr bool KEEP_AL = SOCP_KEEP_AL && NQ * MQ <= 4;
-  d4 AL[KEEP_AL ? MQ : 1][KEEP_AL ? NQ : 1];
-#ifndef SOCP_SMALL_CHOL
-#define SOCP_SMALL_CHOL 1  // 0: Li = H^-1 by the Gauss-Jordan sweep for every shape (A/B builds)
-#endif
   // m <= 16: H = L L' (chol), Z = L^-1 A' in LDS, S = Z'Z; Li is never formed
-  // and its products are triangular solves (trsv_fwd / trsv_bwd).  Larger m
-  // keep the explicit inverse by the sweep.
-  static constexpr bool CHOL = SOCP_SMALL_CHOL && AL_LDS && !KEEP_AL && !XI;
-#ifndef SOCP_INV_CHOL
-#define SOCP_INV_CHOL 1  // 0: the explicit inverses by the Gauss-Jordan sweep (A/B builds)
-#endif
-  // where Li = H^-1 is formed (XI; the m > 16 shapes): from the Cholesky
+  // and its products are triangular solves (trsv_fwd / trsv_bwd).
+  // !CHOL (XI; the m > 16 shapes): Li = H^-1 is formed from the Cholesky
   // factor, Li = L^-T L^-1 (densesolver.jl:47-48, chol_inv), and likewise
-  // S^-1; the SYRK then leaves H in the upper-block form chol() reads
-  static constexpr bool INV_CHOL = SOCP_INV_CHOL && !CHOL;
-  static constexpr bool UPPER_H = CHOL || INV_CHOL;
+  // S^-1.  Either way the SYRK leaves H in the upper-block form chol() reads.
+  static constexpr bool CHOL = AL_LDS && !XI;
 
   __device__ __forceinline__ Small(const SmallArgs& args)
       : a(args), lane(threadIdx.x), g(threadIdx.x >> 4), cl(threadIdx.x & 15),
@@ -1084,7 +1001,7 @@ struct Small {
 #endif
   // ---------------------------------------------------------------- setup
   // O_U + cone(row) * NPAD per k-row (int32, launch-wide: the cone table is
-  // the batch's), for the SYRK's U rows (SOCP_SYRK_UBT shapes)
+  // the batch's), for the SYRK's U rows (Shape::UBT shapes)
   __device__ __forceinline__ int ubt(int row) const { return reinterpret_cast<const int*>(socp_lds + SH::O_UBT)[row]; }
   // The element that lane `ln` holds in slot s.  Pure-slot kernels honour the
   // launch's rotation (SmallArgs::slot_rot, 0 or 64): slot 0 then starts at
@@ -1159,9 +1076,6 @@ struct Small {
   }
 
   bool ko_gloaded = false;
-#ifndef SOCP_SHARED_RESIDENT
-#define SOCP_SHARED_RESIDENT 3  // bit 0: G stays resident, bit 1: A; 0: SOCP_F_SHARED_MATRICES changes the addressing only (A/B builds)
-#endif
   // SOCP_F_SHARED_MATRICES: G (AGPRs) and A (LDS block O_A) hold the batch's
   // one G and A since this wave's first problem.  Nothing else writes them:
   // G's AGPRs are written in load_problem alone, O_A is only read after it.
@@ -1172,7 +1086,7 @@ struct Small {
   // problem loop clang-22 crashes on several of them (the MFMA_FORM fallback of
   // the Makefile would then change how they are built); they change only
   // their addressing and reload the shared G and A per problem, from L2.
-  static constexpr bool RES_G = (SOCP_SHARED_RESIDENT & 1) && MQ < 4, RES_A = (SOCP_SHARED_RESIDENT & 2) && MQ < 4;
+  static constexpr bool RES_G = MQ < 4, RES_A = MQ < 4;
   bool mat_resident = false;
   // lane c < nc: its cone's kind and offset (per-cone work without the table
   // round trips)
@@ -1193,7 +1107,7 @@ struct Small {
     MARK_BEGIN("load_problem");
     LANE_IDS();
     const bool shared = (a.flags & F_SHARED) != 0;
-    const bool keep = SOCP_SHARED_RESIDENT && shared && mat_resident;  // wave-uniform
+    const bool keep = shared && mat_resident;  // wave-uniform
     const bool keep_g = RES_G && keep, keep_a = RES_A && keep;
     bool formed = false;
     const double* Gp = a.G + (shared ? 0 : p * (int64_t)k * n);
@@ -1215,10 +1129,8 @@ struct Small {
     // problem's G (k n doubles): a padding element (row >= k or col >= n)
     // takes an offset past the range and reads 0 -- no address arithmetic in
     // 64 bits, no branch, no mask per element.
-#ifndef SOCP_GLOAD_BATCH
-#define SOCP_GLOAD_BATCH 16
-#endif
-    constexpr int GT = NP * NQ, GB = SOCP_GLOAD_BATCH;
+    constexpr int GLOAD_BATCH = 16;
+    constexpr int GT = NP * NQ, GB = GLOAD_BATCH;
     // (the base made wave-uniform explicitly: a divergent-looking descriptor
     // would be waterfall-looped around every load)
     const uint64_t gpu = (uint64_t)Gp;
@@ -1356,8 +1268,7 @@ struct Small {
 #pragma unroll
             for (int ti = 0; ti < NQ; ++ti)
 #pragma unroll
-              for (int tj = 0; tj <= ti; ++tj) T[tri(ti, tj)] = UPPER_H ? mfma(X[tj], X[ti], T[tri(ti, tj)])
-                                                                      : mfma(X[ti], X[tj], T[tri(ti, tj)]);
+              for (int tj = 0; tj <= ti; ++tj) T[tri(ti, tj)] = mfma(X[tj], X[ti], T[tri(ti, tj)]);
           }
         }
         SCHED_FENCE();
@@ -1753,9 +1664,6 @@ struct Small {
     return __any(dm);
   }
 
-#ifndef SOCP_RESID_SCAL
-#define SOCP_RESID_SCAL 1  // MP_ITER: residuals and compute_scaling interleaved (0: back to back)
-#endif
   // The per-cone SOC branch of compute_scaling (scalings.jl:32-99) on cone lane
   // c = lane, computed on every lane (branch-free: its instructions share the
   // caller's scheduling region) and stored by the SOC cone lanes only.
@@ -1931,7 +1839,7 @@ struct Small {
       // runs the instruction stream it ran before the fusion existed.  With
       // the U parts behind branches inside one shared instance those launches
       // lost 0.2-0.6 ms at C2's shape.
-      if (__builtin_expect(SOCP_FUSE_U && !(SOCP_KO & 4) && a.fuse_u, 0))
+      if (__builtin_expect(!(SOCP_KO & 4) && a.fuse_u, 0))
         gemv_G_r<true, true>(xq, S_, H_, DZ);
       else
         gemv_G_r<true>(xq, S_, H_, DZ);
@@ -2308,8 +2216,7 @@ struct Small {
   }
 
   // U[c,:] = (sum_{i in cone c} w_i G[i,:]) / (1+wb0), w_head = -(1+wb0), w_tail = wb_i
-  // The cone descriptors come from the kernel arguments (scalar loads); the
-  // row steps a cone covers are taken four at a time, their four weight reads
+  // The row steps a cone covers are taken four at a time, their four weight reads
   // issued together (one LDS round trip per four row steps), the weights
   // masked branch-free.
   __device__ __forceinline__ void compute_U() {
@@ -2321,7 +2228,6 @@ struct Small {
 #pragma unroll
       for (int pp = 0; pp < NP; ++pp) wall[pp] = LDS(WB + 4 * pp + g);
     }
-#if SOCP_U_LANECONES
     // every SOC cone's offset, dim, head weight and 1/(1+wb0) on its cone lane
     // (lane c < nc), read in one round trip with the row weights; the loop
     // takes them by readlane (no scalar-memory or LDS wait per cone)
@@ -2340,13 +2246,6 @@ struct Small {
       const int o = __builtin_amdgcn_readlane(ol, c), d = __builtin_amdgcn_readlane(dl, c);
       const double hw = readlane_d(hwl, c);  // the head row's weight
       const double inv = readlane_d(invl, c);
-#else
-    for (int c = 0; c < nc; ++c) {
-      if (a.cones.kind[c] != SOC_K) continue;
-      const int o = a.cones.offs[c], d = a.cones.dim[c];
-      const double hw = -(1.0 + LDS(WB + o));  // the head row's weight
-      const double inv = LDS(cc(CC_I1, c));
-#endif
       const int p0 = o >> 2, p1 = (o + d + 3) >> 2;  // row steps [p0, p1) meet the cone
       double acc[NQ];
 #pragma unroll
@@ -2390,24 +2289,8 @@ struct Small {
   }
 
   // ----------------------------------------------------- H = X'X (+A'A)
-#ifndef SOCP_SYRK_PIPE
-#define SOCP_SYRK_PIPE 2  // 2: row coefficients two steps ahead, U rows one step ahead
-#endif
-#ifndef SOCP_SYRK_M
-#define SOCP_SYRK_M 1
-#define SOCP_SYRK_L 2
-#define SOCP_SYRK_V 8
-#endif
-  // row step pp of X = W^-1 G: X[i,:] = CA_i G[i,:] + CBV_i U[cone(i),:]
-  __device__ __forceinline__ void genX(int pp, double (&X)[NQ]) {
-    LANE_IDS();
-    const int row = 4 * pp + g;
-    const double cav = LDS(CA + row), cbv = LDS(CBV + row);
-    const int cid = ((int)LDS(O_RC + row)) >> 2;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) X[q] = fma(cav, a_get(G[pp][q]), cbv * LDS(O_U + cid * NPAD + 16 * q + cl));
-  }
-  // genX in two halves, for a two-deep pipeline: the row coefficients (and the
+  // row step pp of X = W^-1 G: X[i,:] = CA_i G[i,:] + CBV_i U[cone(i),:],
+  // in two halves, for a two-deep pipeline: the row coefficients (and the
   // cone id that addresses U) first, the U row and the products a step later
   struct XCoef {
     double ca, cb;
@@ -2415,7 +2298,7 @@ struct Small {
   };
   // (UBT shapes: the lane ids of form_H, computed once for the whole product,
   // and the U row from the launch's table)
-  __device__ __forceinline__ XCoef genX_a(int pp, int g_, int cl_) {
+  __device__ __forceinline__ XCoef xcoef(int pp, int g_, int cl_) {
     XCoef c;
     if constexpr (SH::UBT) {
       const int row = 4 * pp + g_;
@@ -2431,7 +2314,7 @@ struct Small {
     }
     return c;
   }
-  __device__ __forceinline__ void genX_b(int pp, const XCoef& c, double (&X)[NQ]) {
+  __device__ __forceinline__ void xrow(int pp, const XCoef& c, double (&X)[NQ]) {
     double u[NQ];
 #pragma unroll
     for (int q = 0; q < NQ; ++q) u[q] = LDS(c.ub + 16 * q);
@@ -2465,7 +2348,7 @@ struct Small {
     for (int ti = 0; ti < NQ; ++ti)
 #pragma unroll
       for (int tj = 0; tj <= ti; ++tj) {
-        const int bi = UPPER_H ? tj : ti, bj = UPPER_H ? ti : tj;
+        const int bi = tj, bj = ti;  // the upper-block form
         const int Cc = 16 * bj + cl;
         double pv[4];
 #pragma unroll
@@ -2534,25 +2417,25 @@ struct Small {
     if (!rows_in_T) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) T[t] = (d4){0.0, 0.0, 0.0, 0.0};
-#if SOCP_SYRK_PIPE == 2
+    // two-deep pipeline: row coefficients two steps ahead, U rows one step ahead
+    constexpr int SYRK_V = 8;  // VALU instructions scheduled behind each of the later MFMAs
     double Xc[NQ];
     XCoef c1;
     {
-      const XCoef c0 = genX_a(0, g, cl);
-      if (NP > 1) c1 = genX_a(1 < NP ? 1 : 0, g, cl);
-      genX_b(0, c0, Xc);
+      const XCoef c0 = xcoef(0, g, cl);
+      if (NP > 1) c1 = xcoef(1 < NP ? 1 : 0, g, cl);
+      xrow(0, c0, Xc);
     }
 #pragma unroll
     for (int pp = 0; pp < NP; ++pp) {
       XCoef c2 = c1;
-      if (pp + 2 < NP) c2 = genX_a(pp + 2 < NP ? pp + 2 : 0, g, cl);
+      if (pp + 2 < NP) c2 = xcoef(pp + 2 < NP ? pp + 2 : 0, g, cl);
       double Xn[NQ];
-      if (pp + 1 < NP) genX_b(pp + 1 < NP ? pp + 1 : 0, c1, Xn);
+      if (pp + 1 < NP) xrow(pp + 1 < NP ? pp + 1 : 0, c1, Xn);
 #pragma unroll
       for (int ti = 0; ti < NQ; ++ti)
 #pragma unroll
-        for (int tj = 0; tj <= ti; ++tj) T[tri(ti, tj)] = UPPER_H ? mfma(Xc[tj], Xc[ti], T[tri(ti, tj)])
-                                                                : mfma(Xc[ti], Xc[tj], T[tri(ti, tj)]);
+        for (int tj = 0; tj <= ti; ++tj) T[tri(ti, tj)] = mfma(Xc[tj], Xc[ti], T[tri(ti, tj)]);  // block (tj, ti)
       if (pp + 1 < NP) {
         // the step's LDS reads behind the first MFMAs, its VALU after them
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -2562,7 +2445,7 @@ struct Small {
 #pragma unroll
         for (int r = 2; r < NT; ++r) {
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x002, SOCP_SYRK_V, 0);
+          __builtin_amdgcn_sched_group_barrier(0x002, SYRK_V, 0);
         }
       }
       SCHED_FENCE();
@@ -2570,45 +2453,6 @@ struct Small {
 #pragma unroll
       for (int q = 0; q < NQ; ++q) Xc[q] = Xn[q];
     }
-#elif SOCP_SYRK_PIPE
-    // software-pipelined: row step pp+1 of X is generated (LDS coefficient
-    // reads, AGPR reads of G, FMAs) while the MFMAs of step pp run, one MFMA
-    // between every few of those instructions
-    double Xc[NQ];
-    genX(0, Xc);
-#pragma unroll
-    for (int pp = 0; pp < NP; ++pp) {
-      double Xn[NQ];
-      if (pp + 1 < NP) genX(pp + 1, Xn);
-#pragma unroll
-      for (int ti = 0; ti < NQ; ++ti)
-#pragma unroll
-        for (int tj = 0; tj <= ti; ++tj) T[tri(ti, tj)] = UPPER_H ? mfma(Xc[tj], Xc[ti], T[tri(ti, tj)])   // block (tj, ti)
-                                                                : mfma(Xc[ti], Xc[tj], T[tri(ti, tj)]);  // block (ti, tj)
-      if (pp + 1 < NP) {
-#pragma unroll
-        for (int r = 0; r < NT; ++r) {
-          __builtin_amdgcn_sched_group_barrier(0x008, SOCP_SYRK_M, 0);  // one MFMA,
-          __builtin_amdgcn_sched_group_barrier(0x100, SOCP_SYRK_L, 0);  // two LDS reads,
-          __builtin_amdgcn_sched_group_barrier(0x002, SOCP_SYRK_V, 0);  // eight VALU (measured: 1/1/3 -0.7 %)
-        }
-      }
-      SCHED_FENCE();
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) Xc[q] = Xn[q];
-    }
-#else
-#pragma unroll
-    for (int pp = 0; pp < NP; ++pp) {
-      double X[NQ];
-      genX(pp, X);
-#pragma unroll
-      for (int ti = 0; ti < NQ; ++ti)
-#pragma unroll
-        for (int tj = 0; tj <= ti; ++tj) T[tri(ti, tj)] = UPPER_H ? mfma(X[tj], X[ti], T[tri(ti, tj)]) : mfma(X[ti], X[tj], T[tri(ti, tj)]);
-      if (pp % 2 == 1) SCHED_FENCE();
-    }
-#endif
     } else {
       // (the tiles pass through a statement of this branch, so that whatever
       // moves them to the row loop's registers sits here, once per problem,
@@ -2630,7 +2474,7 @@ struct Small {
 #pragma unroll
           for (int ti = 0; ti < NQ; ++ti)
 #pragma unroll
-            for (int tj = 0; tj <= ti; ++tj) T[tri(ti, tj)] = UPPER_H ? mfma(Aq[tj], Aq[ti], T[tri(ti, tj)]) : mfma(Aq[ti], Aq[tj], T[tri(ti, tj)]);
+            for (int tj = 0; tj <= ti; ++tj) T[tri(ti, tj)] = mfma(Aq[tj], Aq[ti], T[tri(ti, tj)]);
         }
     }
     if constexpr (QP) add_P();
@@ -2643,20 +2487,10 @@ struct Small {
       }
   }
 
-  // ------------------------------------------------- H^-1 by a block sweep
-  // The inverse Li = H^-1 of densesolver.jl:47-48 (cholesky! + potrs(I)) is
-  // formed by a symmetric Gauss-Jordan sweep with 16x16 pivot tiles P; after
-  // every tile is swept the lower tiles hold -H^-1.  Per tile:
-  //   D = M_PP = L L' (its current Schur complement), W = L^-1 (VALU, below);
-  //   Y_i = W M_Pi                      (i != P, MFMA)
-  //   M_ij -= Y_i' Y_j                  (i, j != P: the Schur update in Gram
-  //                                      form, as accurate as a Cholesky step)
-  //   M_Pi <- W' Y_i = D^-1 M_Pi, M_PP <- -W'W = -D^-1          (MFMA)
-  // Every pivot of D is a Cholesky pivot of H (a Schur complement), so a
-  // pivot <= 0 or NaN fails exactly where LAPACK potrf fails inside
-  // cholesky!.  C/D-tile algebra: lane (g, cl) holds X[g+4r][cl] in register
-  // r, so register s of a tile is the k-step-s operand of mfma_f64_16x16x4,
-  // and sum_s mfma(U[s], V[s]) = U'V for any two tiles U, V.
+  // ------------------------------------------------------- tile algebra
+  // C/D-tile algebra: lane (g, cl) holds X[g+4r][cl] in register r, so
+  // register s of a tile is the k-step-s operand of mfma_f64_16x16x4, and
+  // sum_s mfma(U[s], V[s]) = U'V for any two tiles U, V.
 
   // sum_s mfma(U[s], V[s], C) with the NEG modifiers of gfx950 f64 MFMA
   // (blgp bit 0 negates A, bit 2 negates C)
@@ -2665,136 +2499,6 @@ struct Small {
 #pragma unroll
     for (int s = 0; s < 4; ++s) C = __builtin_amdgcn_mfma_f64_16x16x4f64(U[s], V[s], C, 0, 0, NEG);
     return C;
-  }
-
-  // tile transpose: by MFMA against the identity (X' I), no LDS hand-off, or
-  // through LDS
-  __device__ __forceinline__ d4 ttrans(const d4& X, const d4& Id) {
-#if SOCP_TRANSPOSE_MFMA
-    return mm<0>(X, Id, (d4){0.0, 0.0, 0.0, 0.0});
-#else
-    return transpose(X);
-#endif
-  }
-
-#ifndef SOCP_SWEEP_LOOKAHEAD
-#define SOCP_SWEEP_LOOKAHEAD 1
-#endif
-  // The MFMA work of panel P that the next pivot tile's factorisation does not
-  // wait for: the Gram updates other than tile (P+1, P+1), the new panel tiles
-  // M_Pi and M_PP.  Enumerated at compile time so it can be dealt out between
-  // the row blocks of the next factorisation (look-ahead).
-  struct PanelOp {
-    int kind, i, j;  // 0: M_ij -= Y_i'Y_j, 1: new panel tile i, 2: M_PP = -W'W, -1: none
-  };
-  template <int Q, int P>
-  static constexpr PanelOp panel_op(int idx) {
-    int cnt = 0;
-    for (int i = 0; i < Q; ++i)
-      for (int j = 0; j <= i; ++j) {
-        if (i == P || j == P || (i == P + 1 && j == P + 1)) continue;
-        if (cnt++ == idx) return PanelOp{0, i, j};
-      }
-    for (int i = 0; i < Q; ++i) {
-      if (i == P) continue;
-      if (cnt++ == idx) return PanelOp{1, i, 0};
-    }
-    if (cnt++ == idx) return PanelOp{2, P, P};
-    return PanelOp{-1, 0, 0};
-  }
-  template <int Q, int P>
-  static constexpr int panel_op_count() {
-    int c = 0;
-    while (panel_op<Q, P>(c).kind >= 0) ++c;
-    return c;
-  }
-  template <int Q, int P, int OP>
-  __device__ __forceinline__ static void do_panel_op(d4 (&M)[Q * (Q + 1) / 2], const d4 (&Y)[Q], const d4& W) {
-    constexpr PanelOp o = panel_op<Q, P>(OP);
-    const d4 z = (d4){0.0, 0.0, 0.0, 0.0};
-    if constexpr (o.kind == 0) {
-      M[tri(o.i, o.j)] = mm<1>(Y[o.i], Y[o.j], M[tri(o.i, o.j)]);  // -= Y_i'Y_j
-    } else if constexpr (o.kind == 1) {
-      if constexpr (o.i < P) M[tri(P, o.i)] = mm<0>(W, Y[o.i], z);  // W'Y_i = D^-1 M_Pi
-      else M[tri(o.i, P)] = mm<0>(Y[o.i], W, z);                    // its transpose
-    } else if constexpr (o.kind == 2) {
-      M[tri(P, P)] = mm<1>(W, W, z);  // -W'W = -D^-1
-    }
-  }
-  template <int Q, int P, int LO, int HI>
-  __device__ __forceinline__ static void do_panel_ops(d4 (&M)[Q * (Q + 1) / 2], const d4 (&Y)[Q], const d4& W) {
-    if constexpr (LO < HI) {
-      do_panel_op<Q, P, LO>(M, Y, W);
-      do_panel_ops<Q, P, LO + 1, HI>(M, Y, W);
-    }
-  }
-  // hook for the next factorisation: after row block B, a quarter of the ops
-  template <int Q, int P>
-  struct PanelHook {
-    d4 (&M)[Q * (Q + 1) / 2];
-    const d4 (&Y)[Q];
-    const d4& W;
-    template <int B>
-    __device__ __forceinline__ void run() const {
-      constexpr int N = panel_op_count<Q, P>();
-      do_panel_ops<Q, P, (N * B) / 4, (N * (B + 1)) / 4>(M, Y, W);
-    }
-  };
-
-  // Panel P of the sweep, given W = L^-1 of its pivot tile (factored by the
-  // previous panel, overlapped with that panel's MFMA work).
-  template <int Q, bool SUBST, int P>
-  __device__ __forceinline__ void sweep_panel(d4 (&M)[Q * (Q + 1) / 2], const d4& Id, const d4& W, bool& ok) {
-    MARK_BEGIN("sweep_tiles");
-    if constexpr (P < Q) {
-      d4 X[Q];  // M_Pi in C/D layout (stored transposed below the pivot tile)
-#pragma unroll
-      for (int i = P + 1; i < Q; ++i) X[i] = ttrans(M[tri(i, P)], Id);
-      const d4 WT = ttrans(W, Id);
-      const d4 z = (d4){0.0, 0.0, 0.0, 0.0};
-      d4 Y[Q];
-#pragma unroll
-      for (int i = 0; i < Q; ++i)
-        if (i != P) Y[i] = mm<0>(WT, i < P ? M[tri(P, i)] : X[i], z);  // W M_Pi
-      STAMP_SUB(2);
-      if constexpr (P + 1 < Q) {
-        // the next pivot tile first, then its factorisation with the rest of
-        // this panel's MFMA work dealt out between its row blocks
-        M[tri(P + 1, P + 1)] = mm<1>(Y[P + 1], Y[P + 1], M[tri(P + 1, P + 1)]);
-        d4 Wn;
-#if SOCP_SWEEP_LOOKAHEAD
-        factor_tile<TILE_INPL, TILE_LANES>(M[tri(P + 1, P + 1)], Wn, ok, PanelHook<Q, P>{M, Y, W});
-#else
-        do_panel_ops<Q, P, 0, panel_op_count<Q, P>()>(M, Y, W);
-        factor_tile<TILE_INPL, TILE_LANES>(M[tri(P + 1, P + 1)], Wn, ok);
-#endif
-        STAMP_SUB(1);
-        sweep_panel<Q, SUBST, P + 1>(M, Id, Wn, ok);
-      } else {
-        do_panel_ops<Q, P, 0, panel_op_count<Q, P>()>(M, Y, W);
-        STAMP_SUB(3);
-      }
-    }
-  }
-  template <int Q, bool SUBST>
-  __device__ __forceinline__ void sweep_tiles(d4 (&M)[Q * (Q + 1) / 2], const d4& Id, bool& ok) {
-    d4 W;
-    factor_tile<TILE_INPL, TILE_LANES>(M[tri(0, 0)], W, ok);
-    STAMP_SUB(0);
-    sweep_panel<Q, SUBST, 0>(M, Id, W, ok);
-  }
-
-  // Symmetric sweep of every pivot of M (lower tiles; padding rows carry an
-  // identity diagonal, so sweeping them is harmless): leaves -M^-1.
-  template <int Q, bool SUBST>
-  __device__ __forceinline__ bool sweep(d4 (&M)[Q * (Q + 1) / 2]) {
-    LANE_IDS();
-    d4 Id;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) Id[r] = (g + 4 * r == cl) ? 1.0 : 0.0;
-    bool ok = true;
-    sweep_tiles<Q, SUBST>(M, Id, ok);
-    return ok;
   }
 
   // ------------------------------------ H = L L' by 16x16 tiles (CHOL shapes)
@@ -2808,7 +2512,7 @@ struct Small {
   // Look-ahead: Y_{P+1} and U_{P+1,P+1} first, then the next pivot tile is
   // factored with the rest of the panel's MFMA work -- and the panel's tile
   // row of Z -- dealt out between its row blocks.  Every pivot is a Cholesky
-  // pivot of H (potrf's test, as the sweep's).
+  // pivot of H (potrf's test).
   struct CholOp {
     int kind, i, j;  // 0: Y_i = W_P U_Pi, 1: U_ij -= Y_i'Y_j, 2: the Z row of panel P, -1: none
   };
@@ -2832,8 +2536,8 @@ struct Small {
     return c;
   }
   // Z_P = W_P (A'_P - sum_{Q<P} L_PQ Z_Q) (left-looking: one accumulator tile),
-  // S += Z_P'Z_P (Sv[0]); Z' row-major in LDS at O_AL (where the sweep path
-  // keeps A Li): Z'[c][j] = LDS(O_AL + c*LDA + j).
+  // S += Z_P'Z_P (Sv[0]); Z' row-major in LDS at O_AL (where the explicit-inverse
+  // kernels keep A Li): Z'[c][j] = LDS(O_AL + c*LDA + j).
   template <int P>
   __device__ __forceinline__ void z_row(const d4& WT) {
     LANE_IDS();
@@ -2927,7 +2631,7 @@ struct Small {
   // (3) Li = Y'Y in place, row by row: Li_ab = sum_{q >= a} Y_qa' Y_qb (a >= b),
   //     symmetric by construction.
   // In: M in the upper-block form (M[tri(j, i)] = block (i, j), i <= j, the
-  // SYRK's UPPER_H output); out: the lower tiles of the inverse in the natural
+  // SYRK's output); out: the lower tiles of the inverse in the natural
   // C/D layout (M[tri(a, b)] = block (a, b)), as symv and the record read them.
   struct GCholOp {
     int kind, i, j;  // 0: M_iP = W_P M_iP (= L_iP'), 1: M_ij -= L_iP L_jP', -1: none
@@ -3061,7 +2765,8 @@ struct Small {
         }
   }
 
-  // H (+A'A) -> sweep -> Li;  ALi' = Li A' (n x m);  S = A ALi';  S^-1.
+  // H (+A'A) = L L'.  CHOL: Z = L^-1 A', S = Z'Z, S^-1.  Otherwise Li = L^-T L^-1;
+  // ALi' = Li A' (n x m);  S = A ALi';  S^-1.
   // OV: a kernel with the pipelined load (the only ones that name FAC_IDENT_H)
   template <bool OV = false>
   __device__ __forceinline__ int factor(int kind, bool addAA) {
@@ -3081,11 +2786,11 @@ struct Small {
 #ifdef SOCP_DIAG
     // diagnostic dump per problem: H, H^-1 (n x n each), lam, wbar (k each), Li A' (n x m), S (m x m)
     double* dbg = (a.dbg && a.mode == MODE_KKT) ? a.dbg + dbg_p * (int64_t)(2 * n * n + 2 * k + n * m + m * m) : nullptr;
-    if (dbg && !CHOL) dump_sym(dbg, UPPER_H);
+    if (dbg && !CHOL) dump_sym(dbg, true);
 #endif
     if constexpr (CHOL) {
       const bool okH = chol();
-      STAMP(SP_SWEEP_H);
+      STAMP(SP_FACTOR_H);
       if (!okH) {
         clear_tb();
         return ST_CHOL_H;
@@ -3093,9 +2798,8 @@ struct Small {
 #pragma unroll
       for (int r = 0; r < 4; ++r)
         if (g + 4 * r == cl && cl >= m) Sv[0][r] = 1.0;
-#if SOCP_S_TILE
       // S = L L' on one tile (potrf's pivot test), S^-1 = W'W with W = L^-1:
-      // one MFMA tile chain and four MFMAs instead of the 16-pivot sweep
+      // one MFMA tile chain and four MFMAs
       bool okS = true;
       if (!(SOCP_KO & 8)) {
         d4 Ws;
@@ -3105,29 +2809,13 @@ struct Small {
       clear_tb();
       STAMP(SP_SCHUR);
       if (!okS) return ST_CHOL_S;
-#else
-      const bool okS = (SOCP_KO & 8) ? true : sweep<1, false>(Sv);
-      clear_tb();
-      STAMP(SP_SCHUR);
-      if (!okS) return ST_CHOL_S;
-      Sv[0] = -Sv[0];
-#endif
       return 0;
     }
-    bool okH;
-    if constexpr (INV_CHOL) {
-      okH = chol_inv<NQ>(T);
-    } else {
-      okH = sweep<NQ, true>(T);
-    }
-    STAMP(SP_SWEEP_H);
+    const bool okH = chol_inv<NQ>(T);
+    STAMP(SP_FACTOR_H);
     if (!okH) {
       clear_tb();
       return ST_CHOL_H;
-    }
-    if constexpr (!INV_CHOL) {
-#pragma unroll
-      for (int t = 0; t < NT; ++t) T[t] = -T[t];  // the sweep leaves -H^-1
     }
 #ifdef SOCP_DIAG
     if (dbg) {
@@ -3178,15 +2866,12 @@ struct Small {
 #pragma unroll
           for (int s = 0; s < 4; ++s) {
             const double av = LDS(O_A + (16 * tm + cl) * LDA + 16 * tk + g + 4 * s);
-            // INV_CHOL: block (tq, tm) of S, the upper-block form chol_inv reads
-            acc = INV_CHOL ? mfma(ALc[tk][s], av, acc) : mfma(av, ALc[tk][s], acc);
+            // block (tq, tm) of S, the upper-block form chol_inv reads
+            acc = mfma(ALc[tk][s], av, acc);
           }
         Sv[tri(tm, tq)] = acc;
       }
-      if constexpr (KEEP_AL) {
-#pragma unroll
-        for (int ti = 0; ti < NQ; ++ti) AL[tq][ti] = transpose(ALc[ti]);  // A Li = (Li A')'
-      } else if constexpr (AL_LDS) {
+      if constexpr (AL_LDS) {
         // A Li row-major in LDS: lane (g, cl) holds (A Li)[16tq+cl][16ti+g+4r]
 #pragma unroll
         for (int ti = 0; ti < NQ; ++ti)
@@ -3210,25 +2895,16 @@ struct Small {
         for (int tq = 0; tq <= tm; ++tq)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const int R = (INV_CHOL ? 16 * tq : 16 * tm) + g + 4 * r, Cc = (INV_CHOL ? 16 * tm : 16 * tq) + cl;
+            const int R = 16 * tq + g + 4 * r, Cc = 16 * tm + cl;
             if (R < m && Cc < m) dS[R * m + Cc] = dS[Cc * m + R] = Sv[tri(tm, tq)][r];
           }
     }
 #endif
     SYNC();
-    bool okS;
-    if constexpr (INV_CHOL) {
-      okS = chol_inv<MQ>(Sv);
-    } else {
-      okS = sweep<MQ, false>(Sv);
-    }
-    clear_tb();  // the sweeps' and A Li's transposes ran in the dead k-vectors (TB_ALIAS)
+    const bool okS = chol_inv<MQ>(Sv);
+    clear_tb();  // the factorisations' and A Li's transposes ran in the dead k-vectors (TB_ALIAS)
     STAMP(SP_SCHUR);
     if (!okS) return ST_CHOL_S;
-    if constexpr (!INV_CHOL) {
-#pragma unroll
-      for (int t = 0; t < MT; ++t) Sv[t] = -Sv[t];
-    }
     return 0;
   }
 
@@ -3312,11 +2988,7 @@ struct Small {
   // all-reduce; M'u (u[g+4r] in the lanes of row group g) gives (M'u)[cl]
   // after the four-row sum.  The off-diagonal products of earlier tiles are
   // accumulated lane-locally and reduced once per tile.
-#ifndef SOCP_ALLRED_RS
-#define SOCP_ALLRED_RS 1
-#endif
   __device__ __forceinline__ static void allred16(double (&v)[4]) {
-#if SOCP_ALLRED_RS
     // reduce-scatter (entry r ends in lanes 4r..4r+3 of the row: rs16's base is
     // cl >> 2), then each entry broadcast from lane 4r by row_newbcast: 9 DPP
     // moves and 6 adds per 64-bit lane value instead of 16 and 16
@@ -3328,16 +3000,6 @@ struct Small {
     v[1] = dpp_all<0x154>(t);
     v[2] = dpp_all<0x158>(t);
     v[3] = dpp_all<0x15C>(t);
-#else
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] += row_partner<8>(v[r]);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] += row_partner<4>(v[r]);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] += row_partner<2>(v[r]);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] += row_partner<1>(v[r]);
-#endif
   }
   // out = L^-1 v: t_P = W_P (v_P - sum_{Q<P} L_PQ t_Q).  rc: v in column
   // layout (every lane holds v[16i+cl]); tv: t in row layout (tv[P][r] =
@@ -3575,10 +3237,8 @@ struct Small {
     }
   }
 
-#ifndef SOCP_LDS_BATCH
-#define SOCP_LDS_BATCH 16  // LDS reads issued per round trip in the A products (8 where HOIST_CST is off)
-#endif
-  static constexpr int LDB = HOIST_CST ? SOCP_LDS_BATCH : 8;
+  static constexpr int LDS_BATCH = 16;  // LDS reads issued per round trip in the A products (8 where HOIST_CST is off)
+  static constexpr int LDB = HOIST_CST ? LDS_BATCH : 8;
   static constexpr int AMB = (NQ * 4) % LDB == 0 ? LDB : 4;
   static constexpr int ATB = (MQ * 4) % (LDB / NQ > 0 ? LDB / NQ : 1) == 0 ? (LDB / NQ > 0 ? LDB / NQ : 1) : 1;
   // acc[q] (all lanes) = (A' v)[16q+cl]: rows split over the 4 lane groups
@@ -3589,7 +3249,7 @@ struct Small {
 #pragma unroll
     for (int q = 0; q < NQ; ++q) acc[q] = 0.0;
     // the reads of a step batch issued before its products (one LDS round
-    // trip per SOCP_LDS_BATCH rows, not one per row: the scheduler otherwise
+    // trip per LDB rows, not one per row: the scheduler otherwise
     // interleaves read, wait, fma)
 #pragma unroll
     for (int s0 = 0; s0 < MQ * 4; s0 += ATB) {
@@ -3745,7 +3405,7 @@ struct Small {
     MARK_BEGIN("solve_matrix_part");
     LANE_IDS();
     // n0 in column layout, in every lane (the CHOL path hands it to trsv_fwd_r
-    // in registers; the sweep path's symv reads it from N0)
+    // in registers; the explicit-inverse kernels' symv reads it from N0)
     double n0[NQ];
     {
       double acc[NQ], at[NQ];
@@ -3822,10 +3482,7 @@ struct Small {
       SYNC();
     }
     STAMP_X(6);
-    if constexpr (KEEP_AL) {
-      // cx = Li (n0 + A'm0) = Li n0 + (A Li)' m0
-      ALt_mv(M0, TN, RX);
-    } else if constexpr (AL_LDS) {
+    if constexpr (AL_LDS) {
       // cx = Li (n0 + A'm0) = Li n0 + (A Li)' m0: one Li product per solve
       // (CHOL: cx = L^-T (t + Z m0))
       double at[NQ], tn[NQ];
@@ -3870,28 +3527,6 @@ struct Small {
     }
   }
 
-  // out[j] = add[j] + ((A Li)' v)[j]: per tile column, an in-lane sum over the
-  // tile's rows (registers) and the four row groups (rows_sum)
-  __device__ __forceinline__ void ALt_mv(int v, int add, int out) {
-    LANE_IDS();
-    double vr[MQ][4];
-#pragma unroll
-    for (int tq = 0; tq < MQ; ++tq)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) vr[tq][r] = LDS(v + 16 * tq + g + 4 * r);
-#pragma unroll
-    for (int ti = 0; ti < NQ; ++ti) {
-      double acc = 0.0;
-#pragma unroll
-      for (int tq = 0; tq < MQ; ++tq)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc = fma(AL[KEEP_AL ? tq : 0][KEEP_AL ? ti : 0][r], vr[tq][r], acc);
-      acc = rows_sum(acc);
-      if (g == 0) LDS(out + 16 * ti + cl) = acc + LDS(add + 16 * ti + cl);
-    }
-    SYNC();
-  }
-
   // ------------------------------------------------------- factor record
   // setup_iter's products for the later solve_kkt calls: H^-1 and S^-1 in
   // register-tile (lane) order, the scaling vectors and per-cone constants the
@@ -3902,6 +3537,7 @@ struct Small {
   }
   static constexpr int64_t REC_SING = (int64_t)(NT + MT) * 256 + 5 * KP + 20 * NCS + (AL_LDS ? MPAD * LDA : 0);
   static constexpr int64_t REC_STATUS = REC_SING + 1;  // setup_iter's status, read first by solve_kkt
+  static_assert(REC_SING + 8 == small_rec_doubles(NQ, NP, MQ), "the host's record stride");
   __device__ __forceinline__ void store_record(int64_t p) {
     LANE_IDS();
     double* r = a.rec + p * a.rec_stride;
@@ -4131,7 +3767,7 @@ struct Small {
             break;
           }
           bool dm;
-          if constexpr (SOCP_RESID_SCAL && !(SOCP_KO & (2 | 4096))) {
+          if constexpr (!(SOCP_KO & (2 | 4096))) {  // residuals and compute_scaling interleaved
             // (after the last iteration the scaling is computed too, and unused)
             dm = resid_scaling(nd, np_, gap, ll, dm_aa);
             STAMP(SP_RESID);
@@ -4173,7 +3809,7 @@ struct Small {
           }
           // (rmul!(dx, -1) etc., solver.jl:124: the residuals and ds were stored negated)
           // (fused launches: resid_scaling's G x pass has left this scaling's U in LDS)
-          fac_kind = (SOCP_RESID_SCAL && SOCP_FUSE_U && !(SOCP_KO & (2 | 4 | 4096)) && a.fuse_u) ? FAC_SCALED_U : FAC_SCALED;
+          fac_kind = (!(SOCP_KO & (2 | 4 | 4096)) && a.fuse_u) ? FAC_SCALED_U : FAC_SCALED;
           fac_aa = sing;
           fret = MP_SOLVE_HEAD;
           ret = RET_AFFINE;

@@ -220,16 +220,8 @@ __device__ __forceinline__ double dot_strided(const double* p, int64_t stride, c
 
 // loads in flight per lane in the solve kernel's passes over G (an HBM round
 // trip per SQR_GU elements; 16: -1.3 % solve kernel time at the C2 shape)
-#ifndef SQR_GU
-#define SQR_GU 16
-#endif
+constexpr int SQR_GU = 16;
 
-#ifndef SQR_S_MFMA
-#define SQR_S_MFMA 1  // 0: S = C'C one entry per lane (dot products out of LDS)
-#endif
-#ifndef SQR_S_REGS
-#define SQR_S_REGS 1  // 0: chol(S) in LDS for every m (m <= 16: rows of S in registers)
-#endif
 // 1/sqrt(x) from v_rsq_f64 refined by two Newton steps (to within an ulp or
 // two; x < 0 or NaN gives NaN, which the callers' status checks catch; +-0 and
 // +inf give the IEEE +-inf and 0, not the 0 * inf NaN of the refinement)
@@ -610,7 +602,6 @@ __device__ __forceinline__ void setup_problem(Ctx& C, int64_t p) {
       wsync();
       SQ_STAMP(4);
       double* Sm = lds + L.o_S;
-#if SQR_S_MFMA
       // S = C'C by lower 16 x 16 tiles on f64 MFMA (k-steps of four rows of C)
       {
         const int g = lane >> 4, cl = lane & 15;
@@ -633,14 +624,6 @@ __device__ __forceinline__ void setup_problem(Ctx& C, int64_t p) {
           }
         wsync();
       }
-#else
-      // one entry (r, q), r >= q, per lane: independent dot products
-      for (int e = lane; e < m * m; e += 64) {
-        const int r = e % m, q = e / m;
-        if (r >= q) Sm[q * L.ldm + r] = dot_strided(Cm + r * L.ldl, 1, Cm + q * L.ldl, n);
-      }
-#endif
-#if SQR_S_REGS
       if (m <= 16) {
         // chol(S) with the rows of S in registers (lane i: row i), right-looking
         // as the register Cholesky of H above; the lower triangle back to Sm
@@ -670,9 +653,7 @@ __device__ __forceinline__ void setup_problem(Ctx& C, int64_t p) {
         if (lane < m) lds[L.o_rdgs + lane] = rdv;
         wsync();
         if (bad) status = SQR_CHOL_S;
-      } else
-#endif
-      if (!chol_lds(Sm, L.ldm, m, lds + L.o_rdgs, lane)) status = SQR_CHOL_S;
+      } else if (!chol_lds(Sm, L.ldm, m, lds + L.o_rdgs, lane)) status = SQR_CHOL_S;
       SQ_STAMP(5);
     }
   }
@@ -1301,6 +1282,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NC >= 64 ? 2
   setup_problem<NC>(C, (int64_t)blockIdx.x);
 }
 
+// waves per SIMD the n = 64 solve kernel's registers allow (2: +7 % solve time)
+constexpr int SQR_SOLVE_WPE = 3;
 template <int NC>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NC >= 64 ? SQR_SOLVE_WPE : 3))) void socp_sqr_solve_kernel(SqrArgs a) {
   extern __shared__ double lds_dyn[];
