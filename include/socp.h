@@ -140,6 +140,33 @@ typedef struct socp_params {
  * records stay per problem) and by socp_ingest_create (the matrices are then
  * given by socp_ingest_set_matrices, not per submit). */
 #define SOCP_F_SHARED_MATRICES 512
+/* Equilibration: the solver stops on an absolute test and factors H without
+ * pivoting, so both depend on the units of the caller's rows and columns.
+ * With this flag the problem is first scaled by socp_batch_equilibrate's rule
+ * (below) -- diagonal D, E, F whose entries are powers of two, so scaling and
+ * unscaling are exact in fp64 -- then solved, then unscaled.
+ * Contract: every output (x, y, z, s, iters, status, res, the kernel name) is
+ * bitwise what this pipeline gives:
+ *   1. socp_batch_equilibrate on (P, c, A, b, G, h);
+ *   2. the same solve entry without the flag on the scaled data;
+ *   3. x = D x^, y = E y^, z = F z^, s = F^-1 s^ (ldexp: exact).
+ * It follows that tol, init_eps, the sing == NULL probe and res[] refer to the
+ * SCALED problem: status == 0 still implies res[0] + res[1] + res[2] < tol, in
+ * the scaled units (res[0] is ||D rd||, res[1] is ||E rp|| of the returned
+ * iterate; z's is invariant, and so are G x + s = h up to F, cone membership
+ * and the objective).  A given `sing` is used as given.  The caller's inputs
+ * are never written: the scaled copies live in buffers of the context (with
+ * host pointers, the staged device copy is scaled in place).  The
+ * SOCP_DUMP_DIR dump writes the caller's data.
+ * Honoured through params->flags by socp_batch_solve, socp_batch_solve_ex and
+ * socp_batch_solve_qp.  SOCP_F_FORCE_LARGE, SOCP_F_EXPLICIT_INVERSE and
+ * SOCP_F_SHARED_MATRICES pass through (shared: one scaling for the batch, and
+ * the replicated-bits contract above holds).  With SOCP_F_WARM_START (the
+ * incoming iterate would need scaling) or SOCP_F_DETECT_INFEASIBLE (tau's
+ * meaning would move with the units) the call returns SOCP_E_UNSUPPORTED;
+ * so do socp_ingest_submit[_csc] and socp_sqr_solve_socp for the bit.
+ * Without the flag nothing changes. */
+#define SOCP_F_EQUILIBRATE 1024
 
 typedef struct socp_ctx socp_ctx;
 
@@ -165,6 +192,11 @@ int socp_ctx_reset_stream(socp_ctx* ctx);
  * default is 1e-7 (CVXOPT's feastol).  A non-positive or NaN value returns
  * SOCP_E_INVALID and leaves the tolerance as it was. */
 int socp_ctx_set_infeasibility_tol(socp_ctx* ctx, double tol);
+/* Passes of the equilibration rule (socp_batch_equilibrate, SOCP_F_EQUILIBRATE)
+ * for every later call on the context.  The default is 8: data spread over
+ * 2^+-20 per row and column reaches the rule's fixed point in 6 passes and not
+ * in 4.  A value < 1 or > 64 returns SOCP_E_INVALID and leaves the count as it was. */
+int socp_ctx_set_equilibration_passes(socp_ctx* ctx, int passes);
 
 /* 1 if a compiled kernel accepts the dims: the register-resident kernel (one
  * wavefront per problem, <= 8 cones, m <= 64; k <= 128 for n <= 48, k <= 96
@@ -245,6 +277,37 @@ int socp_batch_solve_qp(socp_ctx* ctx, const socp_dims* dims,
                         const socp_params* params,
                         double* x, double* y, double* z, double* s,
                         int32_t* iters, int32_t* status, double* res);
+
+/* Ruiz equilibration with power-of-two factors, on the device (the reference
+ * has none).  Per matrix set, integer exponents ed[n], ee[m], ef[k] start at 0;
+ * D = 2^ed, E = 2^ee, F = 2^ef.  Each of the context's passes
+ * (socp_ctx_set_equilibration_passes, default 8):
+ *   - scaled magnitudes ldexp(|A_ij|, ee_i + ed_j), ldexp(|G_ij|, ef_i + ed_j)
+ *     and, with a P, ldexp(|P_ij|, ed_i + ed_j);
+ *   - cn_j: the max over column j of all of them; ra_i, rg_i: the max over row
+ *     i of A's and of G's; every row of an SOC cone gets the max of the cone's
+ *     rg (one factor per cone: F s in K <=> s in K); POC rows stay individual;
+ *   - a norm v that is finite and > 0 (subnormals included) gives
+ *     t = -floor((ilogb(v) + 1) / 2), every other norm (zero rows and columns,
+ *     Inf, NaN) t = 0;  ed += t(cn), ee += t(ra), ef += t(rg), each clamped to
+ *     [-256, 256], all three from the same pass's norms.
+ * At the fixed point every norm lies in [1/2, 2).  Outputs:
+ *   D (MB x n), E (MB x m), F (MB x k) doubles, MB = 1 with
+ *   SOCP_F_SHARED_MATRICES and batch otherwise;
+ *   Ps = D P D, As = E A D, Gs = F G D (the layout of the inputs);
+ *   cs = D c, bs = E b, hs = F h (per problem; the one factor set when shared).
+ * Every scaled value is ldexp(value, sum of the exponents): exact, up to one
+ * rounding where a result is subnormal.
+ * P, and A when m = 0, may be NULL.  Any output pointer may be NULL and is then
+ * skipped; c, b, h may be NULL together with their outputs.  The inputs are
+ * not written.  flags: SOCP_F_DEVICE_PTRS (stream-ordered, no synchronisation)
+ * | SOCP_F_SHARED_MATRICES.  The dims gate is socp_supported's. */
+int socp_batch_equilibrate(socp_ctx* ctx, const socp_dims* dims,
+                           const int32_t* cone_kind, const int32_t* cone_offs, const int32_t* cone_dim,
+                           const double* P, const double* c, const double* A, const double* b,
+                           const double* G, const double* h, int32_t flags,
+                           double* D, double* E, double* F,
+                           double* Ps, double* cs, double* As, double* bs, double* Gs, double* hs);
 
 /* Single-problem plugin entries.  They replace the two KKTSolver methods of
  * DenseSolver so the reference's own KKT golden (runtests.jl:95-128) runs

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/socp.h"
+#include "socp_equil.hpp"
 #include "socp_kernels.hpp"
 #include "socp_sqr.hpp"
 
@@ -71,8 +72,12 @@ struct socp_ctx {
   float last_ms = 0.f;
   const char* last_name = "";
   double itol = 1e-7;  // SOCP_F_DETECT_INFEASIBLE's tolerance (socp_ctx_set_infeasibility_tol)
+  int equil_passes = 8;  // SOCP_F_EQUILIBRATE's passes (socp_ctx_set_equilibration_passes)
+  // B_EX: the equilibration exponents; B_E*: the scaled copies of device-pointer inputs, and with
+  // host pointers the staging of socp_batch_equilibrate's D, E, F
   enum { B_C, B_A, B_B, B_G, B_H, B_SING, B_X, B_Y, B_Z, B_S, B_IT, B_ST, B_RES, B_DX, B_DY,
-         B_DZ, B_DS, B_CX, B_CY, B_CZ, B_CS, B_CNT, B_LWS, B_ERR, B_P, NB };
+         B_DZ, B_DS, B_CX, B_CY, B_CZ, B_CS, B_CNT, B_LWS, B_ERR, B_P, B_EX, B_EC, B_EA, B_EB,
+         B_EG, B_EH, B_EP, NB };
   DevBuf buf[NB];
 };
 
@@ -149,6 +154,21 @@ extern "C" int socp_ctx_set_infeasibility_tol(socp_ctx* c, double tol) {
   if (!c) return fail(SOCP_E_INVALID, "ctx is NULL");
   if (!(tol > 0.0)) return fail(SOCP_E_INVALID, "infeasibility tolerance must be positive");  // NaN too
   c->itol = tol;
+  return 0;
+}
+
+extern "C" int socp_ctx_set_equilibration_passes(socp_ctx* c, int passes) {
+  if (!c) return fail(SOCP_E_INVALID, "ctx is NULL");
+  if (passes < 1 || passes > 64) return fail(SOCP_E_INVALID, "equilibration passes must be 1..64");
+  c->equil_passes = passes;
+  return 0;
+}
+
+// SOCP_F_EQUILIBRATE on an entry that does not scale: refused rather than ignored
+static int check_no_equilibrate(int32_t flags, const char* who) {
+  if (flags & SOCP_F_EQUILIBRATE)
+    return fail(SOCP_E_UNSUPPORTED, std::string(who) + ": SOCP_F_EQUILIBRATE is honoured by socp_batch_solve, "
+                                                       "socp_batch_solve_ex and socp_batch_solve_qp only");
   return 0;
 }
 
@@ -574,6 +594,127 @@ static int dump_problems(socp_ctx* ctx, const SmallArgs& a, const double* Pq = n
   return 0;
 }
 
+// ------------------------------------------------------- equilibration
+// socp_equil.hip on device pointers.  equil_matrices: the rule's passes on MB
+// matrix sets; the exponents go to the context's B_EX buffer (MB x (n+m+k)
+// int32, *ex), the factors and the scaled matrices where a pointer is given
+// (a scaled matrix may be its own input).
+static int equil_matrices(socp_ctx* ctx, const ConeTable& cones, int n, int m, int k, int nc, size_t MB,
+                          const double* Pd, const double* Ad, const double* Gd, double* D, double* E, double* F,
+                          double* Ps, double* As, double* Gs, const int32_t** ex) {
+  const size_t S = (size_t)n + m + k;
+  if (ctx->buf[socp_ctx::B_EX].ensure(MB * S * sizeof(int32_t))) return fail(SOCP_E_NOMEM, "device allocation failed");
+  EquilArgs e;
+  memset(&e, 0, sizeof(e));
+  e.A = m > 0 ? Ad : nullptr;
+  e.G = Gd;
+  e.P = Pd;
+  e.As = m > 0 ? As : nullptr;
+  e.Gs = Gs;
+  e.Ps = Pd ? Ps : nullptr;
+  e.D = D;
+  e.E = m > 0 ? E : nullptr;
+  e.F = F;
+  e.ex = (int32_t*)ctx->buf[socp_ctx::B_EX].p;
+  e.n = n;
+  e.m = m;
+  e.k = k;
+  e.nc = nc;
+  e.passes = ctx->equil_passes;
+  e.cones = cones;
+  HIPCHK(equil_launch(e, (int64_t)MB, ctx->stream));
+  *ex = e.ex;
+  return 0;
+}
+
+// dst = ldexp(src, sign * exponent) on up to four batch-major vectors; `which`
+// picks each vector's exponents: 0 ed (length n), 1 ee (m), 2 ef (k).  NULL
+// vectors are skipped.
+struct EquilVec {
+  double* dst;
+  const double* src;
+  int which;
+  int sign;
+};
+static int equil_vectors(socp_ctx* ctx, int n, int m, int k, int64_t B, bool shared, const int32_t* ex,
+                         const EquilVec* v, int cnt) {
+  const int len[3] = {n, m, k}, at[3] = {0, n, n + m};
+  EquilVecArgs va;
+  memset(&va, 0, sizeof(va));
+  va.B = B;
+  va.exstride = shared ? 0 : (int64_t)n + m + k;
+  for (int i = 0; i < cnt; ++i) {
+    if (!v[i].dst || !v[i].src || len[v[i].which] == 0) continue;
+    EquilVecSeg& s = va.seg[va.nseg++];
+    s.dst = v[i].dst;
+    s.src = v[i].src;
+    s.ex = ex + at[v[i].which];
+    s.len = len[v[i].which];
+    s.sign = v[i].sign;
+  }
+  HIPCHK(equil_vec_launch(va, ctx->stream));
+  return 0;
+}
+
+extern "C" int socp_batch_equilibrate(socp_ctx* ctx, const socp_dims* dims, const int32_t* cone_kind,
+                                      const int32_t* cone_offs, const int32_t* cone_dim, const double* Pm,
+                                      const double* c, const double* A, const double* b, const double* G,
+                                      const double* h, int32_t flags, double* D, double* E, double* F, double* Ps,
+                                      double* cs, double* As, double* bs, double* Gs, double* hs) {
+  if (!ctx) return fail(SOCP_E_INVALID, "ctx is NULL");
+  ConeTable cones;
+  memset(&cones, 0, sizeof(cones));
+  int degree = 0;
+  TRY(check_problem(dims, cone_kind, cone_offs, cone_dim, &cones, &degree));
+  if (flags & ~(SOCP_F_DEVICE_PTRS | SOCP_F_SHARED_MATRICES))
+    return fail(SOCP_E_INVALID, "socp_batch_equilibrate: flags other than SOCP_F_DEVICE_PTRS | SOCP_F_SHARED_MATRICES");
+  const int64_t B = dims->batch;
+  const int n = dims->n, m = dims->m, k = dims->k;
+  if (!socp_supported(dims)) return fail(SOCP_E_UNSUPPORTED, kUnsupported);
+  if (B == 0) return 0;
+  if (!G || (m > 0 && !A)) return fail(SOCP_E_INVALID, "NULL data pointer");
+  if ((cs && !c) || (bs && !b) || (hs && !h) || (Ps && !Pm))
+    return fail(SOCP_E_INVALID, "a scaled output without its input");
+  HIPCHK(hipSetDevice(ctx->device));
+  const bool dev = (flags & SOCP_F_DEVICE_PTRS) != 0;
+  const bool shared = (flags & SOCP_F_SHARED_MATRICES) != 0;
+  const size_t MB = shared ? 1 : (size_t)B;
+  typedef socp_ctx X;
+  // host pointers: inputs staged as a solve stages them and scaled in place; D, E, F through B_EC, B_EB, B_EH
+  const double *Pd = nullptr, *cd = nullptr, *Ad = nullptr, *bd = nullptr, *Gd = nullptr, *hd = nullptr;
+  TRY(stage_in(ctx, X::B_P, Pm, MB * n * n, dev, &Pd));
+  TRY(stage_in(ctx, X::B_C, cs ? c : nullptr, (size_t)B * n, dev, &cd));
+  TRY(stage_in(ctx, X::B_A, m > 0 ? A : nullptr, MB * m * n, dev, &Ad));
+  TRY(stage_in(ctx, X::B_B, bs ? b : nullptr, (size_t)B * m, dev, &bd));
+  TRY(stage_in(ctx, X::B_G, G, MB * k * n, dev, &Gd));
+  TRY(stage_in(ctx, X::B_H, hs ? h : nullptr, (size_t)B * k, dev, &hd));
+  double *Dd = nullptr, *Ed = nullptr, *Fd = nullptr;
+  TRY(stage_out(ctx, X::B_EC, D, MB * n, dev, false, &Dd));
+  TRY(stage_out(ctx, X::B_EB, E, MB * m, dev, false, &Ed));
+  TRY(stage_out(ctx, X::B_EH, F, MB * k, dev, false, &Fd));
+  double* Psd = !Ps ? nullptr : dev ? Ps : const_cast<double*>(Pd);
+  double* Asd = !As ? nullptr : dev ? As : const_cast<double*>(Ad);
+  double* Gsd = !Gs ? nullptr : dev ? Gs : const_cast<double*>(Gd);
+  double* csd = !cs ? nullptr : dev ? cs : const_cast<double*>(cd);
+  double* bsd = !bs ? nullptr : dev ? bs : const_cast<double*>(bd);
+  double* hsd = !hs ? nullptr : dev ? hs : const_cast<double*>(hd);
+  const int32_t* ex = nullptr;
+  TRY(equil_matrices(ctx, cones, n, m, k, dims->ncones, MB, Pd, Ad, Gd, Dd, Ed, Fd, Psd, Asd, Gsd, &ex));
+  const EquilVec fw[3] = {{csd, cd, 0, 1}, {bsd, bd, 1, 1}, {hsd, hd, 2, 1}};
+  TRY(equil_vectors(ctx, n, m, k, B, shared, ex, fw, 3));
+  TRY(copy_back(ctx, D, Dd, MB * n, dev));
+  TRY(copy_back(ctx, E, Ed, MB * m, dev));
+  TRY(copy_back(ctx, F, Fd, MB * k, dev));
+  TRY(copy_back(ctx, Ps, Psd, MB * n * n, dev));
+  TRY(copy_back(ctx, cs, csd, (size_t)B * n, dev));
+  TRY(copy_back(ctx, As, Asd, MB * m * n, dev));
+  TRY(copy_back(ctx, bs, bsd, (size_t)B * m, dev));
+  TRY(copy_back(ctx, Gs, Gsd, MB * k * n, dev));
+  TRY(copy_back(ctx, hs, hsd, (size_t)B * k, dev));
+  if (!dev) HIPCHK(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
 // socp_batch_solve_ex, and with Pm != NULL socp_batch_solve_qp: the QP solver
 // kernels with the objective x'Px/2 + c'x
 static int batch_solve_impl(socp_ctx* ctx, const socp_dims* dims, const int32_t* cone_kind,
@@ -604,6 +745,14 @@ static int batch_solve_impl(socp_ctx* ctx, const socp_dims* dims, const int32_t*
     return fail(SOCP_E_UNSUPPORTED,
                 "socp_batch_solve_qp with SOCP_F_DETECT_INFEASIBLE: the unboundedness rule would also need Px = 0, "
                 "which the detecting kernels do not test");
+  const bool eq = (P.flags & SOCP_F_EQUILIBRATE) != 0;
+  if (eq && (P.flags & SOCP_F_WARM_START))
+    return fail(SOCP_E_UNSUPPORTED,
+                "SOCP_F_EQUILIBRATE with SOCP_F_WARM_START: the incoming iterate would have to be scaled as well");
+  if (eq && (P.flags & SOCP_F_DETECT_INFEASIBLE))
+    return fail(SOCP_E_UNSUPPORTED,
+                "SOCP_F_EQUILIBRATE with SOCP_F_DETECT_INFEASIBLE: the meaning of the infeasibility tolerance would "
+                "move with the scaling");
   if (B == 0) return 0;
   if (!c || !G || !h || !x || !z || !s || !iters || !status || (m > 0 && (!A || !b || !y)))
     return fail(SOCP_E_INVALID, "NULL data pointer");
@@ -627,7 +776,7 @@ static int batch_solve_impl(socp_ctx* ctx, const socp_dims* dims, const int32_t*
   a.tol = P.tol;
   a.step = P.step;
   a.init_eps = P.init_eps;
-  a.flags = P.flags;
+  a.flags = P.flags & ~SOCP_F_EQUILIBRATE;  // (the kernels run what they run without the flag)
   a.mode = MODE_SOLVE;
   a.deg = degree;
   if (P.flags & SOCP_F_DETECT_INFEASIBLE) small_set_itol(a, ctx->itol);
@@ -652,8 +801,39 @@ static int batch_solve_impl(socp_ctx* ctx, const socp_dims* dims, const int32_t*
   TRY(stage_out(ctx, X::B_RES, res, (size_t)B * 3, dev, false, &a.res));
   if (ctx->buf[X::B_CNT].ensure(256)) return fail(SOCP_E_NOMEM, "device allocation failed");
   a.counter = (int32_t*)ctx->buf[X::B_CNT].p;
-  TRY(dump_problems(ctx, a, Pd));
+  TRY(dump_problems(ctx, a, Pd));  // (the caller's data: before any scaling)
+  const int32_t* ex = nullptr;
+  if (eq) {
+    // SOCP_F_EQUILIBRATE: the solver reads scaled copies -- context buffers beside the caller's
+    // device data, or the staged copy of host data scaled in place
+    double* sc[6] = {const_cast<double*>(a.c), const_cast<double*>(a.A), const_cast<double*>(a.b),
+                     const_cast<double*>(a.G), const_cast<double*>(a.h), const_cast<double*>(Pd)};
+    if (dev) {
+      const int slot[6] = {X::B_EC, X::B_EA, X::B_EB, X::B_EG, X::B_EH, X::B_EP};
+      const size_t cnt[6] = {(size_t)B * n, MB * m * n, (size_t)B * m, MB * k * n, (size_t)B * k,
+                             qp ? MB * n * n : 0};
+      for (int i = 0; i < 6; ++i) {
+        if (cnt[i] == 0) continue;
+        if (ctx->buf[slot[i]].ensure(cnt[i] * sizeof(double))) return fail(SOCP_E_NOMEM, "device allocation failed");
+        sc[i] = (double*)ctx->buf[slot[i]].p;
+      }
+    }
+    TRY(equil_matrices(ctx, a.cones, n, m, k, a.nc, MB, Pd, a.A, a.G, nullptr, nullptr, nullptr, sc[5], sc[1], sc[3],
+                       &ex));
+    const EquilVec fw[3] = {{sc[0], a.c, 0, 1}, {sc[2], a.b, 1, 1}, {sc[4], a.h, 2, 1}};
+    TRY(equil_vectors(ctx, n, m, k, B, MB == 1 && (P.flags & SOCP_F_SHARED_MATRICES), ex, fw, 3));
+    a.c = sc[0];
+    a.A = sc[1];
+    a.b = sc[2];
+    a.G = sc[3];
+    a.h = sc[4];
+    if (qp) small_set_qp(a, sc[5]);
+  }
   TRY(v ? launch_small(ctx, a, v, qp) : launch_large(ctx, a, nullptr, qp));
+  if (eq) {  // x = D x^, y = E y^, z = F z^, s = F^-1 s^
+    const EquilVec bw[4] = {{a.x, a.x, 0, 1}, {a.y, a.y, 1, 1}, {a.z, a.z, 2, 1}, {a.s, a.s, 2, -1}};
+    TRY(equil_vectors(ctx, n, m, k, B, (P.flags & SOCP_F_SHARED_MATRICES) != 0, ex, bw, 4));
+  }
   TRY(copy_back(ctx, x, a.x, (size_t)B * n, dev));
   TRY(copy_back(ctx, y, a.y, (size_t)B * m, dev));
   TRY(copy_back(ctx, z, a.z, (size_t)B * k, dev));
@@ -1242,6 +1422,7 @@ extern "C" int socp_sqr_solve_socp(socp_sqr* h, const double* c, const double* b
   if (params) P = *params; else socp_params_default(&P);
   if (P.maxit < 0) return fail(SOCP_E_INVALID, "maxit < 0");
   TRY(check_detect_flags(P.flags));
+  TRY(check_no_equilibrate(P.flags, "socp_sqr_solve_socp"));
   if (sqr_ipm_lds_bytes(n, m, k) > 160 * 1024)
     return fail(SOCP_E_UNSUPPORTED, "socp_sqr_solve_socp: the IPM kernels' vectors (7 k + n + m doubles) exceed 160 KiB");
   socp_ctx* ctx = h->ctx;
@@ -1968,6 +2149,7 @@ extern "C" int socp_ingest_submit(socp_ingest* g, int64_t batch, const double* c
                                   const double* G, const double* h, const uint8_t* sing, const socp_params* params,
                                   int64_t* ticket) {
   if (params) TRY(check_detect_flags(params->flags));
+  if (params) TRY(check_no_equilibrate(params->flags, "socp_ingest_submit"));
   IngestSlot* slp = nullptr;
   TRY(ingest_begin(g, batch, &slp));
   IngestSlot& sl = *slp;
@@ -2021,6 +2203,7 @@ extern "C" int socp_ingest_submit_csc(socp_ingest* g, int64_t batch, const doubl
                                       const double* G_nzval, int32_t index_base, const socp_params* params,
                                       int64_t* ticket) {
   if (params) TRY(check_detect_flags(params->flags));
+  if (params) TRY(check_no_equilibrate(params->flags, "socp_ingest_submit"));
   if (g && g->shared) return fail(SOCP_E_INVALID, "socp_ingest_submit_csc on a SOCP_F_SHARED_MATRICES ingest");
   IngestSlot* slp = nullptr;
   TRY(ingest_begin(g, batch, &slp));

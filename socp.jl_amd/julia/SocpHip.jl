@@ -31,6 +31,7 @@ const SOCP_F_DETECT_INFEASIBLE = Int32(256)
 # One A, one G and one sing byte for every problem of the batch (parametric
 # batches); the outputs are bitwise those of the replicated call (include/socp.h)
 const SOCP_F_SHARED_MATRICES = Int32(512)
+const SOCP_F_EQUILIBRATE = Int32(1024)
 const SOCP_PRIMAL_INFEASIBLE = Int32(5)
 const SOCP_DUAL_INFEASIBLE = Int32(6)
 "tau of the detection rule for every later solve of this process's context (default 1e-7)."
@@ -288,10 +289,14 @@ throwing, so one bad problem does not abort the batch.  With
 are the ray) instead of running to `maxit`.  With `shared_matrices=true` (a
 parametric batch) every problem's `A`, `G` and `sing` must equal the first's
 (`ArgumentError` otherwise) and one copy of them goes to the device
-(`SOCP_F_SHARED_MATRICES`).
+(`SOCP_F_SHARED_MATRICES`).  With `equilibrate=true` (`SOCP_F_EQUILIBRATE`) the
+problems are scaled on the device by power-of-two Ruiz factors, solved and
+unscaled exactly; `tol` then refers to the scaled problem and `sing` is probed
+on the scaled `G`.  Not together with `detect_infeasible`.
 """
 function solve_socp_batched(problems::AbstractVector{<:Problem}; maxit=40, tol=1e-5, explicit_inverse::Bool=false,
-                            detect_infeasible::Bool=false, shared_matrices::Bool=false)
+                            detect_infeasible::Bool=false, shared_matrices::Bool=false,
+                            equilibrate::Bool=false)
     p0 = problems[1]
     n, m, k = p0.n, p0.m, p0.k
     B = length(problems)
@@ -307,7 +312,8 @@ function solve_socp_batched(problems::AbstractVector{<:Problem}; maxit=40, tol=1
     iters, status = zeros(Int32, B), zeros(Int32, B)
     flags = (explicit_inverse ? SOCP_F_EXPLICIT_INVERSE : Int32(0)) |
             (detect_infeasible ? SOCP_F_DETECT_INFEASIBLE : Int32(0)) |
-            (shared_matrices ? SOCP_F_SHARED_MATRICES : Int32(0))
+            (shared_matrices ? SOCP_F_SHARED_MATRICES : Int32(0)) |
+            (equilibrate ? SOCP_F_EQUILIBRATE : Int32(0))
     params = Ref(SocpParams(maxit, 3, tol, 0.99, 1e-10, flags, 0))
     dims = Ref(SocpDims(B, n, m, k, length(p0.cones)))
     rc = ccall((:socp_batch_solve, libsocp), Cint,
@@ -315,7 +321,7 @@ function solve_socp_batched(problems::AbstractVector{<:Problem}; maxit=40, tol=1
                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8},
                 Ref{SocpParams}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
                 Ptr{Int32}, Ptr{Int32}),
-               socp_ctx(), dims, kind, offs, dim, c, A, b, G, h, sing, params,
+               socp_ctx(), dims, kind, offs, dim, c, A, b, G, h, equilibrate ? C_NULL : sing, params,
                x, y, z, s, iters, status)
     socp_check(rc)
     states = [State(problems[i], x[(i-1)*n+1:i*n], y[(i-1)*m+1:i*m], z[(i-1)*k+1:i*k], s[(i-1)*k+1:i*k])

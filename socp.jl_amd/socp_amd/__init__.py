@@ -21,7 +21,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import (CHOL_H_FAILED, CHOL_S_FAILED, CONE_POC, CONE_SOC, CONVERGED, DOMAIN_ERROR, DUAL_INFEASIBLE,
-                   F_DETECT_INFEASIBLE, F_DEVICE_PTRS, F_EXPLICIT_INVERSE, F_FORCE_LARGE, F_SHARED_MATRICES,
+                   F_DETECT_INFEASIBLE, F_DEVICE_PTRS, F_EQUILIBRATE, F_EXPLICIT_INVERSE, F_FORCE_LARGE,
+                   F_SHARED_MATRICES,
                    F_WARM_START, MAXIT,
                    PRIMAL_INFEASIBLE, Context, SocpError,
                    default_context,
@@ -31,7 +32,7 @@ __all__ = [
     "POC", "SOC", "Problem", "State", "Scaling", "DenseSolver", "HipDenseSolver", "SolverState",
     "solve_socp", "solve_socp_batched", "compute_scaling", "setup_iter", "solve_kkt",
     "PosDefException", "DomainError", "batch_solve", "batch_kkt_solve", "DenseHandle", "Ingest",
-    "generate", "pack_csc",
+    "generate", "pack_csc", "equilibrate",
     "Context", "SocpError", "default_context", "cone_arrays",
     "CONVERGED", "MAXIT", "CHOL_H_FAILED", "CHOL_S_FAILED", "DOMAIN_ERROR",
     "PRIMAL_INFEASIBLE", "DUAL_INFEASIBLE",
@@ -137,7 +138,8 @@ def _check_sizes(B, **arrays):
 
 def batch_solve(cones, n, m, k, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5, step=0.99,
                 sigma_exp=3, init_eps=1e-10, warm=None, ctx=None, res=False, out=None, force_large=False,
-                explicit_inverse=False, detect_infeasible=False, shared_matrices=False, P=None):
+                explicit_inverse=False, detect_infeasible=False, shared_matrices=False, P=None,
+                equilibrate=False):
     """Solve a batch of independent problems (same dims and cone structure).
 
     Arrays follow include/socp.h: per-problem column-major A (m x n), G (k x n)
@@ -166,6 +168,12 @@ def batch_solve(cones, n, m, k, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5,
     that makes H indefinite gives that problem CHOL_H_FAILED.  Not together
     with explicit_inverse or detect_infeasible (SOCP_E_UNSUPPORTED).  P=None
     is the plain call.
+    equilibrate (SOCP_F_EQUILIBRATE): scale the problem on the device by
+    ``equilibrate``'s power-of-two factors, solve, and unscale exactly -- the
+    outputs are bitwise those of that three-step pipeline.  tol, init_eps, the
+    sing=None probe and res then refer to the scaled problem; the inputs are
+    not written.  Not together with warm or detect_infeasible
+    (SOCP_E_UNSUPPORTED).
     Returns dict(x, y, z, s, iters, status[, res]).
     """
     L = _lib.load()
@@ -202,6 +210,8 @@ def batch_solve(cones, n, m, k, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5,
         flags |= F_DETECT_INFEASIBLE
     if shared_matrices:
         flags |= F_SHARED_MATRICES
+    if equilibrate:
+        flags |= F_EQUILIBRATE
     pr = default_params(maxit=maxit, tol=tol, step=step, sigma_exp=sigma_exp, init_eps=init_eps,
                         flags=flags)
     if dev:
@@ -247,6 +257,61 @@ def batch_solve(cones, n, m, k, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5,
     _lib.check(rc)
     if not dev and m == 0:
         out["y"] = out["y"][:0]
+    return out
+
+
+def equilibrate(cones, n, m, k, A, G, P=None, c=None, b=None, h=None, *, shared_matrices=False, ctx=None):
+    """Power-of-two Ruiz equilibration of a batch on the device
+    (socp_batch_equilibrate; the rule is in include/socp.h).  A (m x n; None
+    when m = 0), G (k x n) and P (n x n, optional) are column-major and stacked
+    batch-major, ONE of each with shared_matrices; c, b, h are optional.  numpy
+    inputs go through host staging and the call synchronises; torch CUDA
+    tensors are used in place, stream-ordered.  The inputs are not written.
+    Returns a dict with D (MB x n), E (MB x m), F (MB x k) -- MB is 1 with
+    shared_matrices, else the batch -- and the scaled As = E A D, Gs = F G D,
+    and Ps = D P D, cs = D c, bs = E b, hs = F h for the inputs given.  The
+    batch is taken from c, b or h when one is given, else from G."""
+    L = _lib.load()
+    kind, offs, dim = cone_arrays(cones)
+    given = [(v, q) for v, q in ((c, n), (b, m), (h, k)) if v is not None and q]
+    if given:
+        B = _size(given[0][0]) // given[0][1]
+    elif shared_matrices:
+        B = 1
+    else:
+        B = _size(G) // (k * n)
+    MB = 1 if shared_matrices else B
+    _check_sizes(B, A=(A if m else None, MB * m * n), G=(G, MB * k * n), P=(P, MB * n * n), c=(c, B * n),
+                 b=(b if m else None, B * m), h=(h, B * k))
+    dev = _is_torch(G)
+    ctx = ctx or default_context()
+    ins = dict(P=P, c=c, A=A if m else None, b=b if m else None, G=G, h=h)
+    sizes = dict(D=MB * n, E=MB * m, F=MB * k)
+    if dev:
+        import torch
+        ctx.bind_torch_stream()
+        new = lambda cnt: torch.empty(max(cnt, 1), dtype=torch.float64, device=G.device)[:cnt]  # noqa: E731
+        for key, v in ins.items():
+            if v is not None and (not _is_torch(v) or str(v.dtype) != "torch.float64" or v.device != G.device
+                                  or not v.is_contiguous()):
+                raise ValueError(f"{key} must be a contiguous float64 tensor on G's device")
+    else:
+        new = lambda cnt: np.zeros(cnt)  # noqa: E731
+        ins = {key: _host(v) for key, v in ins.items()}
+    out = {key: new(cnt) for key, cnt in sizes.items()}
+    for key, v in ins.items():
+        if v is not None:
+            out[key + "s"] = new(_size(v))
+    p = _lib.ptr
+    dims = _lib.Dims(B, n, m, k, len(kind))
+    flags = (F_DEVICE_PTRS if dev else 0) | (F_SHARED_MATRICES if shared_matrices else 0)
+
+    def po(key):  # NULL for an absent or empty array
+        v = out.get(key)
+        return p(v) if v is not None and _size(v) else None
+    _lib.check(L.socp_batch_equilibrate(
+        ctx.handle, dims, p(kind), p(offs), p(dim), p(ins["P"]), p(ins["c"]), p(ins["A"]), p(ins["b"]), p(ins["G"]),
+        p(ins["h"]), flags, po("D"), po("E"), po("F"), po("Ps"), po("cs"), po("As"), po("bs"), po("Gs"), po("hs")))
     return out
 
 
@@ -869,7 +934,7 @@ def solve_socp(prob: Problem, ss: SolverState) -> State:
 
 
 def solve_socp_batched(problems, maxit=40, tol=1e-5, ctx=None, solver="dense", detect_infeasible=False,
-                       shared_matrices=False):
+                       shared_matrices=False, equilibrate=False):
     """Batched solve of Problems sharing dims and cones; returns (states, iters, status)
     without raising: failures are reported per problem.  solver="dense": the
     DenseSolver path (the fused register / blocked kernels); "sqr": the
@@ -880,7 +945,8 @@ def solve_socp_batched(problems, maxit=40, tol=1e-5, ctx=None, solver="dense", d
     otherwise); one copy of them goes to the device (SOCP_F_SHARED_MATRICES).
     When any problem carries a P the batch runs the QP entry (``batch_solve``'s
     P; dense solver only); problems without one get zeros, and with
-    shared_matrices every P must equal the first's as well."""
+    shared_matrices every P must equal the first's as well.  equilibrate as in
+    ``batch_solve`` (dense solver only); `sing` is then probed on the scaled G."""
     p0 = problems[0]
     n, m, k = p0.n, p0.m, p0.k
     for p in problems:
@@ -907,13 +973,16 @@ def solve_socp_batched(problems, maxit=40, tol=1e-5, ctx=None, solver="dense", d
         if solver == "sqr":
             raise ValueError("P: the rank-update solver takes linear objectives only")
         P = np.concatenate([_colmajor(p.P, n, n) if p.P is not None else np.zeros(n * n) for p in mats])
+    if equilibrate and solver == "sqr":
+        raise ValueError("equilibrate: the rank-update solver does not scale (SOCP_E_UNSUPPORTED)")
     if solver == "sqr":
         out = SqrHandle(p0.cones, n, m, k, A, G, sing, ctx=ctx, shared_matrices=shared_matrices,
                         batch=len(problems)).solve_socp(
             c, b, h, maxit=maxit, tol=tol, detect_infeasible=detect_infeasible)
     else:
-        out = batch_solve(p0.cones, n, m, k, c, A, b, G, h, sing, maxit=maxit, tol=tol, ctx=ctx,
-                          detect_infeasible=detect_infeasible, shared_matrices=shared_matrices, P=P)
+        out = batch_solve(p0.cones, n, m, k, c, A, b, G, h, None if equilibrate else sing, maxit=maxit, tol=tol,
+                          ctx=ctx, detect_infeasible=detect_infeasible, shared_matrices=shared_matrices, P=P,
+                          equilibrate=equilibrate)
     states = [State(p, out["x"][i * n:(i + 1) * n], out["y"][i * m:(i + 1) * m],
                     out["z"][i * k:(i + 1) * k], out["s"][i * k:(i + 1) * k])
               for i, p in enumerate(problems)]

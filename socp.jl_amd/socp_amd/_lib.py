@@ -22,6 +22,7 @@ CONE_POC, CONE_SOC = 0, 1
 F_DEVICE_PTRS, F_WARM_START, F_FORCE_LARGE, F_EXPLICIT_INVERSE = 1, 2, 4, 8
 F_DETECT_INFEASIBLE = 256  # bits 16..128 are the CPU oracle's
 F_SHARED_MATRICES = 512  # one A, G, sing for the whole batch (SOCP_F_SHARED_MATRICES)
+F_EQUILIBRATE = 1024  # power-of-two Ruiz scaling before the solve, exact unscaling after (SOCP_F_EQUILIBRATE)
 
 EXPORTED = [
     "socp_last_error", "socp_version", "socp_params_default", "socp_ctx_create",
@@ -37,7 +38,7 @@ EXPORTED = [
     "socp_sqr_supported", "socp_sqr_create", "socp_sqr_setup_iter", "socp_sqr_solve_kkt", "socp_sqr_factor",
     "socp_sqr_scaling", "socp_sqr_h2d_bytes", "socp_sqr_record_bytes", "socp_sqr_destroy",
     "socp_sqr_solve_socp", "socp_ctx_set_infeasibility_tol", "socp_debug_slot_plan",
-    "socp_batch_solve_qp",
+    "socp_batch_solve_qp", "socp_batch_equilibrate", "socp_ctx_set_equilibration_passes",
 ]
 
 OUTCOME_BYTES = 32  # sizeof(socp_outcome): int32 status, int32 iters, double rd, rp, gap
@@ -101,6 +102,10 @@ def load():
     L.socp_ctx_reset_stream.argtypes = [vp]
     if hasattr(L, "socp_ctx_set_infeasibility_tol"):  # infeasibility detection (absent from older A/B builds)
         L.socp_ctx_set_infeasibility_tol.argtypes = [vp, C.c_double]
+    if hasattr(L, "socp_batch_equilibrate"):  # equilibration (absent from older A/B builds)
+        L.socp_ctx_set_equilibration_passes.argtypes = [vp, C.c_int]
+        L.socp_batch_equilibrate.argtypes = ([vp, C.POINTER(Dims), i32p, i32p, i32p] + [dp] * 6 + [C.c_int32]
+                                             + [dp] * 9)
     L.socp_supported.argtypes = [C.POINTER(Dims)]
     if hasattr(L, "socp_debug_slot_plan"):  # (absent from older A/B builds)
         L.socp_debug_slot_plan.argtypes = [C.POINTER(Dims), i32p, i32p, i32p] + [C.POINTER(C.c_int32)] * 3
@@ -221,6 +226,12 @@ class Context:
         for every later solve on this context; default 1e-7
         (socp_ctx_set_infeasibility_tol).  Non-positive or NaN raises."""
         check(load().socp_ctx_set_infeasibility_tol(self.handle, float(tol)))
+
+    def set_equilibration_passes(self, passes: int) -> None:
+        """Passes of the equilibration rule (equilibrate, batch_solve(...,
+        equilibrate=True)) for every later call on this context; default 8
+        (socp_ctx_set_equilibration_passes).  Below 1 or above 64 raises."""
+        check(load().socp_ctx_set_equilibration_passes(self.handle, int(passes)))
 
     def last_kernel_ms(self) -> float:
         v = C.c_float()

@@ -135,7 +135,8 @@ class ModelData:
 
 class Optimizer:
     """`Socp.Optimizer` (moi.jl:57-66) over the GPU dense path.  Keyword options:
-    `maxit` (default 40, solver.jl:105), `tol` (1e-5, solver.jl:122), `ctx`."""
+    `maxit` (default 40, solver.jl:105), `tol` (1e-5, solver.jl:122), `ctx`,
+    `equilibrate` (default False; `optimize_batched`)."""
 
     def __init__(self, **options):
         self.options = dict(options)
@@ -299,15 +300,21 @@ def optimize_batched(optimizers, ctx=None, shared_matrices=False):
     (SOCP_F_DETECT_INFEASIBLE).  Per-model options `maxit`/`tol` must agree within a group.
     shared_matrices=True: a parametric batch -- within every group each model's A
     and G (and with them `sing`) must equal the group's first (ValueError
-    otherwise), and one copy of them goes to the device (SOCP_F_SHARED_MATRICES)."""
+    otherwise), and one copy of them goes to the device (SOCP_F_SHARED_MATRICES).
+    Models built with `Optimizer(equilibrate=True)` form groups of their own and
+    are solved with SOCP_F_EQUILIBRATE (``batch_solve``'s equilibrate: `tol`
+    then refers to the scaled problem, and `sing` is probed on the scaled G).
+    The library refuses detection together with that flag, so these groups run
+    without it: an infeasible model ends with a numerical status, not a certificate."""
     groups: "OrderedDict[tuple, list]" = OrderedDict()
     for o in optimizers:
         d = o.build()
-        key = d.signature + (int(o.options.get("maxit", 40)), float(o.options.get("tol", 1e-5)))
+        key = d.signature + (int(o.options.get("maxit", 40)), float(o.options.get("tol", 1e-5)),
+                             bool(o.options.get("equilibrate", False)))
         groups.setdefault(key, []).append(o)
     for key, opts in groups.items():
         n, f, l, qa = key[:4]
-        maxit, tol = key[4], key[5]
+        maxit, tol, equil = key[4], key[5], key[6]
         k = l + sum(qa)
         ds = [o.data for o in opts]
         if shared_matrices:
@@ -315,14 +322,14 @@ def optimize_batched(optimizers, ctx=None, shared_matrices=False):
                 if (f and not np.array_equal(d.A, ds[0].A)) or not np.array_equal(d.G, ds[0].G):
                     raise ValueError(f"shared_matrices=True: model {i} of its group differs from the first in A or G")
         ms = ds[:1] if shared_matrices else ds
-        sing = np.array([_sing(d.G) for d in ms], np.uint8)
+        sing = None if equil else np.array([_sing(d.G) for d in ms], np.uint8)
         c = np.concatenate([d.c for d in ds])
         A = np.concatenate([d.A.ravel(order="F") for d in ms]) if f else None
         b = np.concatenate([d.b for d in ds]) if f else None
         G = np.concatenate([d.G.ravel(order="F") for d in ms])
         h = np.concatenate([d.h for d in ds])
-        out = batch_solve(ds[0].cones, n, f, k, c, A, b, G, h, sing, maxit=maxit, tol=tol, detect_infeasible=True,
-                          shared_matrices=shared_matrices,
+        out = batch_solve(ds[0].cones, n, f, k, c, A, b, G, h, sing, maxit=maxit, tol=tol,
+                          detect_infeasible=not equil, equilibrate=equil, shared_matrices=shared_matrices,
                           ctx=ctx if ctx is not None else opts[0].options.get("ctx"))
         for i, o in enumerate(opts):
             o._set_solution(out["x"][i * n:(i + 1) * n], out["y"][i * f:(i + 1) * f],
