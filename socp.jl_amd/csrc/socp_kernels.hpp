@@ -1,6 +1,10 @@
-// socp_kernels.hpp — internal launch interface between socp_api.hip and the
+// socp_kernels.hpp — internal launch interface between the C ABI units and the
 // kernels: the register-resident instantiations (gen_inst.py) and the blocked
-// kernel (socp_large.hip).
+// kernel (socp_large.hip).  Both are launched by socp_api.hip alone (launch_small,
+// launch_large; socp_host.hpp declares them for the dense-handle and ingest
+// units).  socp_api_sqr.hip launches socp_sqr.hip's and socp_sqr_ipm.hip's
+// kernels (socp_sqr.hpp), socp_api.hip socp_equil.hip's (socp_equil.hpp), and
+// socp_api_gen.hip its own.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "socp_small.hpp"

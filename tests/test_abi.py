@@ -69,6 +69,33 @@ def test_null_context_is_an_api_error():
     assert b"ctx" in L.socp_last_error()
 
 
+def test_last_error_is_shared_across_units_and_per_thread():
+    """One argument check in each unit of the C ABI shim (socp_api*.hip): every unit writes the one
+    thread-local string that socp_last_error() returns."""
+    import threading
+    L = _lib.load()
+    d = _lib.Dims(1, 3, 0, 4, 2)
+    handle = C.c_void_p()
+    calls = (  # (unit, call, text); consecutive texts differ
+        ("socp_api", lambda: L.socp_batch_solve(None, C.byref(d), *[None] * 16), b"ctx is NULL"),
+        ("socp_api_dense", lambda: L.socp_dense_setup_iter(None, None, None, None), b"handle is NULL"),
+        ("socp_api_gen", lambda: L.socp_pack_csc(None, 1, 1, 1, None, None, None, None, 0, None), b"ctx is NULL"),
+        ("socp_api_sqr", lambda: L.socp_sqr_h2d_bytes(None, None), b"NULL argument"),
+        ("socp_api_ingest", lambda: L.socp_ingest_create(None, C.byref(d), None, None, None, 0, C.byref(handle)),
+         b"ctx is NULL"),
+        ("socp_api_comm", lambda: L.socp_comm_unique_id(None), b"id is NULL"),
+    )
+    for unit, call, text in calls:
+        assert call() == _lib.SOCP_E_INVALID, unit
+        assert L.socp_last_error() == text, unit
+    seen = []
+    t = threading.Thread(target=lambda: seen.append(L.socp_last_error()))
+    t.start()
+    t.join()
+    assert seen == [b""]  # another thread has its own, still empty, string
+    assert L.socp_last_error() == b"id is NULL"
+
+
 def test_problem_mirror_asserts_and_sing(kats):
     # Problem(c, A, b, G, h, cones): shape asserts (Socp.jl:43-47) and `sing` (Socp.jl:49-56)
     cones, c, A, b, G, h = kat_problem(kats["soc3"])

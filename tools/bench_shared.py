@@ -14,7 +14,7 @@ tol 0.  Prints
      arrays in, results out), shared against replicated, over
      --ingest-batches batches, with the input bytes per batch;
   4. the device and pinned bytes socp_ingest_create and socp_dense_create
-     allocate in both forms, computed from the layouts (socp_api.hip).
+     allocate in both forms, computed from the layouts (socp_api_ingest.hip, socp_api_dense.hip).
 """
 import argparse
 import os

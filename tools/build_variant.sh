@@ -2,7 +2,8 @@
 # Tuning builds (never the product): the C1/C2 register-kernel instantiations
 # (gen_inst.py SOCP_DEV_VARIANTS) compiled with extra flags, linked with the
 # product build's other objects into socp.jl_amd/lib/v_<name>/libsocp.so.
-# The compile flags and the list of those objects come from the Makefile.
+# The compile flags and the lists of the API units and of those objects come
+# from the Makefile.
 #   tools/build_variant.sh <name> "<extra hipcc flags>"
 set -e
 name=$1; extra=$2
@@ -23,11 +24,16 @@ for f in $GEN/inst_*.hip; do
   $HIPCC $FLAGS -c $f -o $OBJ/$b.o > $OBJ/$b.log 2>&1 &
   pids+=($!)
 done
-# the C ABI too (host-side layout helpers such as small_lds_bytes see the flags)
-$HIPCC $FLAGS -c $C/socp_api.hip -o $OBJ/socp_api.o > $OBJ/socp_api.log 2>&1 &
-pids+=($!)
+# the C ABI units too (host-side layout helpers such as small_lds_bytes see the flags)
+AOBJS=
+for o in $(mk print-API_OBJS); do
+  b=${o%.o}
+  $HIPCC $FLAGS -c $C/$b.hip -o $OBJ/$o > $OBJ/$b.log 2>&1 &
+  pids+=($!)
+  AOBJS="$AOBJS $OBJ/$o"
+done
 for p in "${pids[@]}"; do wait $p || { echo "compile failed"; cat $OBJ/*.log | tail -20; exit 1; }; done
 M=$R/socp.jl_amd/build/obj
 KOBJS=$(for o in $(mk print-KERNEL_OBJS); do echo $M/$o; done)
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o $LIB/libsocp.so $OBJ/socp_api.o $KOBJS $OBJ/inst_*.o
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o $LIB/libsocp.so $AOBJS $KOBJS $OBJ/inst_*.o
 echo "built $LIB/libsocp.so"
