@@ -104,6 +104,44 @@ def order_floor_traces(oracle, cones, c, A, b, G, h, K, flags, seeds=(1, 2, 3), 
     return base, floor
 
 
+def one_step_references(oracle, cones, c, A, b, G, h, flags, seeds=range(1, 9), maxit=40, tol=1e-5, steps=None):
+    """One oracle step from every iterate of the oracle's own solve of one
+    problem under the reference rule (maxit, tol; sing = False) in operation
+    order `flags`, and what one rounding does to that step.  steps: indices
+    into the solve's iterates (negative ones count from the last), None for all.
+    Per chosen iterate t a dict:
+      t        the iterate's index; last: it is the one the solve ended at
+      iterate  (x, y, z, s) at the start of iteration t -- the step's warm start
+      status   of one step from it (Params(maxit=1, tol=0.0, flags=flags)):
+               1 the step was taken, 2 / 3 / 4 chol(H) / chol(S) / domain failed
+      next     the step's (x, z, s)
+      replay   (x, z, s) of iterate t + 1 of the solve (None at the last)
+      decided  the step ends with the same status on perturb_G(G, seed), every seed
+      floor    {"x", "z", "s"}: the largest relative change of `next` over the
+               seeds; None unless the step was taken on G and on every perturbed G
+    A step is not chaotic the way a trajectory is: it replays the solve's next
+    iterate exactly, and its floor is that of one KKT factorisation."""
+    r = oracle.solve_trace(cones, c, A, b, G, h, sing=False, params=oracle.Params(maxit=maxit, tol=tol, flags=flags),
+                           max_trace=maxit + 1)
+    its = list(r["trace"][:r["iters"]]) + [(r["x"], r["y"], r["z"], r["s"])]
+    P1 = oracle.Params(maxit=1, tol=0.0, flags=flags)
+    pert = [perturb_G(G, sd) for sd in seeds]
+    out = []
+    for t in (range(len(its)) if steps is None else sorted(t % len(its) for t in steps)):
+        one = [oracle.solve_trace(cones, c, A, b, Gx, h, sing=False, params=P1, max_trace=2, warm=its[t])
+               for Gx in [G] + pert]
+        base, status = one[0], [o["status"] for o in one]
+        floor = None
+        if all(st == 1 for st in status):
+            floor = {key: max(float(np.linalg.norm(base[key] - o[key]) / np.linalg.norm(base[key])) for o in one[1:])
+                     for key in "xzs"}
+        nxt = its[t + 1] if t + 1 < len(its) else None
+        out.append(dict(t=t, last=nxt is None, iterate=its[t], status=status[0], next=tuple(base[key] for key in "xzs"),
+                        replay=None if nxt is None else (nxt[0], nxt[2], nxt[3]),
+                        decided=all(st == status[0] for st in status), floor=floor))
+    return out
+
+
 # A kernel-order iterate may differ from the oracle's in the same order by the
 # rounding of a different summation order; its floor is the oracle's own
 # sensitivity to one rounding (every G entry +-1 ulp, three seeds).  The gate is
