@@ -994,8 +994,9 @@ struct Small {
 
 #ifndef SOCP_KO
 #define SOCP_KO 0  // timing knock-outs (tuning builds only; results are wrong): 1 G loaded once per wave,
-                   // 2 no residuals, 4 no U (neither compute_U nor the residuals' fused form), 8 no S factorisation, 16 no Gx, 32 no G'z (residuals),
-                   // 128 no A products (residuals), 256 no triangular solves, 512 / 1024 no G products
+                   // 2 no residuals, 4 no U (neither compute_U nor the residuals' fused form), 8 no S factorisation,
+                   // 16 no Gx (so no fused U either: the factorisation then runs compute_U), 32 no G'z, 128 no A products
+                   // (the three of resid_scaling_k's residual half), 256 no triangular solves, 512 / 1024 no G products
                    // in the solves, 2048 no S solves, 4096 no scaling, 8192 no solve head,
                    // 16384 no solve tail, 32768 no corrector, 65536 no SYRK (H = I), 131072 no chol
 #endif
@@ -1538,6 +1539,11 @@ struct Small {
   // Two segmented reductions; the SOC cone math (norms, gamma, mu, lambda_0 and
   // the coefficients of the tail rows) runs once per cone on lane c, not once
   // per element.
+  // For MP_KKT only.  These are the operations of resid_scaling_k's scaling
+  // half (its scaling-only instantiation is what a SOCP_KO 2 build runs), kept
+  // as a body of its own: every solver kernel compiles MP_KKT, and with that
+  // instantiation laid into them in this body's place C2's solves ran 1 %
+  // slower, though a solve never enters it.
   __device__ __forceinline__ bool scaling_op(double& ll, bool& dm_aa, bool write_ds) {
     SOCP_SLOT_DISPATCH(scaling_op_k, ll, dm_aa, write_ds);
   }
@@ -1731,102 +1737,135 @@ struct Small {
   // scheduling regions: the scaling's cone-lane chains (rsqrt / recip
   // latency on three lanes) run inside the residuals' G'z pass and beside
   // their G x pass (VALU issue), the element part beside the A products (LDS
-  // latency).  The same operations as residuals() then scaling_op(): the
-  // results are bitwise the same.  Returns the DomainError flag.
+  // latency).  The only copy of the residuals, and the iteration's only copy
+  // of the scaling (MP_KKT has scaling_op).  RESID / SCAL pick the halves that
+  // run: the SOCP_KO 2 / 4096 builds drop the residuals / the scaling -- each
+  // half's operations, and so its bits, are those of the interleaved pass.
+  // Returns the DomainError flag.
+  template <bool RESID = true, bool SCAL = true>
   __device__ __forceinline__ bool resid_scaling(double& nd, double& np_, double& gap, double& ll, bool& dm_aa) {
-    SOCP_SLOT_DISPATCH(resid_scaling_k, nd, np_, gap, ll, dm_aa);
+    return resid_scaling_k<KS0, KS1, RESID, SCAL>(nd, np_, gap, ll, dm_aa);
   }
-  template <int SL0, int SL1>
+  template <int SL0, int SL1, bool RESID, bool SCAL>
   __device__ __forceinline__ bool resid_scaling_k(double& nd, double& np_, double& gap, double& ll, bool& dm_aa) {
     MARK_BEGIN("resid_scaling");
     LANE_IDS();
     constexpr int NS = KP > 64 ? 2 : 1;
+    // rd = A'y + G'z + c (QP: + Px), rp = Ax - b, rz = Gx + s - h (solver.jl:109-118):
+    // the small operands read up front, in one round trip: c and x (column
+    // layout), z and s (slot layout)
     double cq[NQ], xq[NQ], zv[NS], sv[NS];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      cq[q] = LDS(C_ + 16 * q + cl);
-      xq[q] = LDS(X_ + 16 * q + cl);
-    }
-#pragma unroll
-    for (int t = 0; t < NS; ++t) {  // z's: summed over the fixed pairing 64 t + lane, rotated slots or not
-      zv[t] = LDS(Z_ + 64 * t + lane);
-      sv[t] = LDS(S_ + 64 * t + lane);
-    }
     double pq[NQ];  // QP: (P x)[16q+cl], formed first, while few registers are live
-    if constexpr (QP) P_mv(X_, pq);
+    if constexpr (RESID) {
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        cq[q] = LDS(C_ + 16 * q + cl);
+        xq[q] = LDS(X_ + 16 * q + cl);
+      }
+#pragma unroll
+      for (int t = 0; t < NS; ++t) {  // z's: summed over the fixed pairing 64 t + lane, rotated slots or not
+        zv[t] = LDS(Z_ + 64 * t + lane);
+        sv[t] = LDS(S_ + 64 * t + lane);
+      }
+      if constexpr (QP) P_mv(X_, pq);
+    }
     // ---- scaling, first reduction: |z_1|^2, |s_1|^2, z_1's_1 per cone
     double v[2][3], zi[2], si[2];
+    if constexpr (SCAL) {
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const int i = el(s, lane);
-      zi[s] = LDS(Z_ + i);
-      si[s] = LDS(S_ + i);
-      const bool tail = tailm(SOCP_SK(s), kd[s]);
-      v[s][0] = tail ? zi[s] * zi[s] : 0.0;
-      v[s][1] = tail ? si[s] * si[s] : 0.0;
-      v[s][2] = tail ? zi[s] * si[s] : 0.0;
+      for (int s = 0; s < 2; ++s) {
+        const int i = el(s, lane);
+        zi[s] = LDS(Z_ + i);
+        si[s] = LDS(S_ + i);
+        const bool tail = tailm(SOCP_SK(s), kd[s]);
+        v[s][0] = tail ? zi[s] * zi[s] : 0.0;
+        v[s][1] = tail ? si[s] * si[s] : 0.0;
+        v[s][2] = tail ? zi[s] * si[s] : 0.0;
+      }
+      cone_partials<3, may_soc(SL0) ? 7u : 0u, may_soc(SL1) ? 7u : 0u>(v);
     }
-    cone_partials<3, may_soc(SL0) ? 7u : 0u, may_soc(SL1) ? 7u : 0u>(v);
-    // ---- the cone-lane chain inside G'z's first batch
+    // ---- the cone-lane chain inside G'z's first batch (on its own where no G'z pass runs)
     const bool socl = HOIST_CST ? lc_soc : (lane < nc && (int)LDS(O_CKIND + lane) == SOC_K);
     const int cc_ = lane < nc ? lane : 0;
     const int oc = socl ? (HOIST_CST ? lc_off : (int)LDS(O_COFF + lane)) : 0;
     ScalCone1 c1;
     double acc[NQ], at[NQ];
-    gemv_Gt(Z_, acc, ScalHook{*this, c1, oc, cc_});
-    if (socl) scal_cone1_store(c1, oc, cc_);
-    bool dm = socl && c1.dm;
-    SYNC();
-    // ---- the elements (POC, scalings.jl:22-30; SOC tails) beside A'y
-    MARK_BEGIN("scal_elem");
-    double li[2], wbi[2];
+    if constexpr (!RESID || (SOCP_KO & 32)) {
+      if constexpr (SCAL) c1 = scal_cone1_math(oc, cc_);
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-#pragma clang fp contract(off)
-      const int i = el(s, lane), c = ci[s];
-      const bool poc = pocs(SOCP_SK(s), kd[s]), pm = pocm(SOCP_SK(s), kd[s]), tail = tailm(SOCP_SK(s), kd[s]);
-      const double pr = si[s] * zi[s];
-      const double q = rsqrt_nr(pr);
-      const double as = ccv(CC_AS, c), az = ccv(CC_AZ, c), bs = ccv(CC_BS, c), bz = ccv(CC_BZ, c);
-      const double imu = ccv(CC_IMU, c), l0 = ccv(CC_L0, c);
-      const double wt = fma(si[s], as, -(zi[s] * az));
-      const double lt = fma(si[s], bs, zi[s] * bz);
-      dm = dm || (pm && pr < 0.0);
-      wbi[s] = poc ? zmul(si[s], q) : (tail ? wt : ccv(CC_WB0, c));
-      li[s] = poc ? zmul(pr, q) : (tail ? lt : l0);
-      if (pm || tail) {
-        LDS(WB + i) = wbi[s];
-        LDS(LAM + i) = li[s];
-        LDS(CA + i) = poc ? zmul(zi[s], q) : imu;
-        LDS(CBV + i) = poc ? 0.0 : wt * imu;
-        if (pm) LDS(IL + i) = q;
-        LDS(DS + i) = -(poc ? li[s] * li[s] : fma(l0, li[s], l0 * li[s]));  // -ds: the RHS
-      }
-      v[s][0] = (pm || tail) ? li[s] * li[s] : 0.0;
-      v[s][1] = tail ? wbi[s] * wbi[s] : 0.0;
-      v[s][2] = tail ? wbi[s] * li[s] : 0.0;
+      for (int q = 0; q < NQ; ++q) acc[q] = 0.0;
+    } else if constexpr (SCAL) {
+      gemv_Gt(Z_, acc, ScalHook{*this, c1, oc, cc_});
+    } else {
+      gemv_Gt(Z_, acc);
     }
-    At_mv(Y_, at);
-    cone_partials<3, may_soc(SL0) ? 7u : 1u, may_soc(SL1) ? 7u : 1u>(v);
-    // ---- rd, the second cone-lane part beside A x and G x + s - h
-    double d2 = 0.0, zs = 0.0;
-    if (g == 0) {
+    bool dm = false;
+    if constexpr (SCAL) {
+      if (socl) scal_cone1_store(c1, oc, cc_);
+      dm = socl && c1.dm;
+      SYNC();
+      // ---- the elements (POC, scalings.jl:22-30; SOC tails) beside A'y
+      MARK_BEGIN("scal_elem");
+      double li[2], wbi[2];
 #pragma unroll
-      for (int q = 0; q < NQ; ++q) {
-        const int j = 16 * q + cl;
-        if (j < n) {
-          double vv = (at[q] + acc[q]) + cq[q];
-          if constexpr (QP) vv += pq[q];
-          LDS(RD + j) = -vv;  // the residuals are stored negated: the affine RHS (solver.jl:124)
-          d2 = fma(vv, vv, d2);
+      for (int s = 0; s < 2; ++s) {
+#pragma clang fp contract(off)
+        const int i = el(s, lane), c = ci[s];
+        const bool poc = pocs(SOCP_SK(s), kd[s]), pm = pocm(SOCP_SK(s), kd[s]), tail = tailm(SOCP_SK(s), kd[s]);
+        // POC: one 1/sqrt(s z) gives sqrt(s/z) = s q, sqrt(z/s) = z q, sqrt(s z) = (s z) q
+        const double pr = si[s] * zi[s];
+        const double q = rsqrt_nr(pr);
+        const double as = ccv(CC_AS, c), az = ccv(CC_AZ, c), bs = ccv(CC_BS, c), bz = ccv(CC_BZ, c);
+        const double imu = ccv(CC_IMU, c), l0 = ccv(CC_L0, c);
+        const double wt = fma(si[s], as, -(zi[s] * az));
+        const double lt = fma(si[s], bs, zi[s] * bz);
+        dm = dm || (pm && pr < 0.0);
+        wbi[s] = poc ? zmul(si[s], q) : (tail ? wt : ccv(CC_WB0, c));
+        li[s] = poc ? zmul(pr, q) : (tail ? lt : l0);
+        if (pm || tail) {
+          LDS(WB + i) = wbi[s];
+          LDS(LAM + i) = li[s];
+          LDS(CA + i) = poc ? zmul(zi[s], q) : imu;
+          LDS(CBV + i) = poc ? 0.0 : wt * imu;
+          if (pm) LDS(IL + i) = q;
+          LDS(DS + i) = -(poc ? li[s] * li[s] : fma(l0, li[s], l0 * li[s]));  // -ds: the RHS
+        }
+        // lam o lam head (vprod!, vectors.jl:58-75) and |lambda_1|^2 (POC: the
+        // cone's sum of lambda_i^2, its share of lam'lam), |wbar_1|^2, wbar_1'lambda_1
+        v[s][0] = (pm || tail) ? li[s] * li[s] : 0.0;
+        v[s][1] = tail ? wbi[s] * wbi[s] : 0.0;
+        v[s][2] = tail ? wbi[s] * li[s] : 0.0;
+      }
+    }
+    if constexpr (RESID && !(SOCP_KO & 128)) {
+      At_mv(Y_, at);
+    } else {
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) at[q] = 0.0;
+    }
+    if constexpr (SCAL) cone_partials<3, may_soc(SL0) ? 7u : 1u, may_soc(SL1) ? 7u : 1u>(v);
+    // ---- rd, the second cone-lane part beside A x and G x + s - h
+    double d2 = 0.0, p2 = 0.0, zs = 0.0;
+    if constexpr (RESID) {
+      if (g == 0) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+          const int j = 16 * q + cl;
+          if (j < n) {
+            double vv = (at[q] + acc[q]) + cq[q];
+            if constexpr (QP) vv += pq[q];
+            LDS(RD + j) = -vv;  // the residuals are stored negated: the affine RHS (solver.jl:124)
+            d2 = fma(vv, vv, d2);
+          }
         }
       }
+      if constexpr (!(SOCP_KO & 128)) p2 = A_mv(X_, B_, RP, O_A, true);
     }
-    const double p2 = A_mv(X_, B_, RP, O_A, true);
     bool da = false;
     double tl = 0.0;
     {
       MARK_BEGIN("scal_cone2");
+      // (computed on every lane, stored by the SOC cone lanes; without SCAL nothing below uses them)
       const double l1 = cone_tot(0, cc_);
       const double l0 = LDS(cc(CC_L0, cc_));
       const double aa = l0 * l0 - l1;
@@ -1839,38 +1878,46 @@ struct Small {
       // runs the instruction stream it ran before the fusion existed.  With
       // the U parts behind branches inside one shared instance those launches
       // lost 0.2-0.6 ms at C2's shape.
-      if (__builtin_expect(!(SOCP_KO & 4) && a.fuse_u, 0))
-        gemv_G_r<true, true>(xq, S_, H_, DZ);
-      else
-        gemv_G_r<true>(xq, S_, H_, DZ);
-      if (lane < nc) {
-        if (socl) {
-          da = aa < 0.0;
-          LDS(cc(CC_W2, cc_)) = w2;
-          LDS(cc(CC_WL, cc_)) = wl;
-          LDS(cc(CC_AA, cc_)) = aa;
-          LDS(cc(CC_IAA, cc_)) = iaa;
-          LDS(cc(CC_IL0, cc_)) = il0;
-          LDS(cc(CC_IL0AA, cc_)) = il0aa;
-          LDS(cc(CC_SA, cc_)) = sa;
-          LDS(cc(CC_SAL, cc_)) = sal;
-          tl = l0 * l0 + l1;
-          LDS(DS + oc) = -tl;
-        } else {
-          tl = l1;
+      if constexpr (RESID && !(SOCP_KO & 16)) {
+        if (__builtin_expect(SCAL && !(SOCP_KO & 4) && a.fuse_u, 0))
+          gemv_G_r<true, true>(xq, S_, H_, DZ);
+        else
+          gemv_G_r<true>(xq, S_, H_, DZ);
+      }
+      if constexpr (SCAL) {
+        if (lane < nc) {
+          if (socl) {
+            da = aa < 0.0;
+            LDS(cc(CC_W2, cc_)) = w2;
+            LDS(cc(CC_WL, cc_)) = wl;
+            LDS(cc(CC_AA, cc_)) = aa;
+            LDS(cc(CC_IAA, cc_)) = iaa;
+            LDS(cc(CC_IL0, cc_)) = il0;
+            LDS(cc(CC_IL0AA, cc_)) = il0aa;
+            LDS(cc(CC_SA, cc_)) = sa;
+            LDS(cc(CC_SAL, cc_)) = sal;
+            tl = l0 * l0 + l1;
+            LDS(DS + oc) = -tl;
+          } else {
+            tl = l1;
+          }
         }
       }
     }
     SYNC();
+    if constexpr (RESID) {
 #pragma unroll
-    for (int t = 0; t < NS; ++t)
-      if (64 * t + lane < k) zs = fma(zv[t], sv[t], zs);  // (explicit: every instantiation sums z's alike, socp_batch_solve_qp's res at P = 0 included)
-    double r3[3] = {d2, p2, zs};  // the three whole-wave sums in one interleaved scan
-    dpp_scan<3>(r3, lane, 0, false);
-    nd = sqrt(readlane_d(r3[0], 63));
-    np_ = sqrt(readlane_d(r3[1], 63));
-    gap = readlane_d(r3[2], 63);
-    ll = wsum(tl);
+      for (int t = 0; t < NS; ++t)
+        if (64 * t + lane < k) zs = fma(zv[t], sv[t], zs);  // (explicit: every instantiation sums z's alike, socp_batch_solve_qp's res at P = 0 included)
+      double r3[3] = {d2, p2, zs};  // the three whole-wave sums in one interleaved scan
+      dpp_scan<3>(r3, lane, 0, false);
+      nd = sqrt(readlane_d(r3[0], 63));
+      np_ = sqrt(readlane_d(r3[1], 63));
+      gap = readlane_d(r3[2], 63);
+    } else {
+      nd = np_ = gap = 1.0;
+    }
+    ll = SCAL ? wsum(tl) : 1.0;
     dm_aa = __any(da);
     return __any(dm);
   }
@@ -3337,66 +3384,6 @@ struct Small {
     return sq;
   }
 
-  // rd = A'y + G'z + c (QP: + Px), rp = Ax - b, rz = Gx + s - h (solver.jl:109-118)
-  __device__ __forceinline__ void residuals(double& nd, double& np_, double& gap) {
-    MARK_BEGIN("residuals");
-    LANE_IDS();
-    double acc[NQ], at[NQ];
-    // the small operands read up front, in one round trip: c and x (column
-    // layout), z and s (slot layout)
-    constexpr int NS = KP > 64 ? 2 : 1;
-    double cq[NQ], xq[NQ], zv[NS], sv[NS];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      cq[q] = LDS(C_ + 16 * q + cl);
-      xq[q] = LDS(X_ + 16 * q + cl);
-    }
-#pragma unroll
-    for (int t = 0; t < NS; ++t) {
-      zv[t] = LDS(Z_ + 64 * t + lane);
-      sv[t] = LDS(S_ + 64 * t + lane);
-    }
-    double pq[NQ];  // QP: (P x)[16q+cl], formed first, while few registers are live
-    if constexpr (QP) P_mv(X_, pq);
-    if (SOCP_KO & 32) {
-      for (int q = 0; q < NQ; ++q) acc[q] = 0.0;
-    } else {
-      gemv_Gt(Z_, acc);
-    }
-    if (SOCP_KO & 128) {
-      for (int q = 0; q < NQ; ++q) at[q] = 0.0;
-    } else {
-      At_mv(Y_, at);
-    }
-    double d2 = 0.0, zs = 0.0;
-    if (g == 0) {
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) {
-        const int j = 16 * q + cl;
-        if (j < n) {
-          double v = (at[q] + acc[q]) + cq[q];
-          if constexpr (QP) v += pq[q];
-          LDS(RD + j) = -v;  // the residuals are stored negated: the affine RHS (solver.jl:124)
-          d2 = fma(v, v, d2);
-        }
-      }
-    }
-    const double p2 = (SOCP_KO & 128) ? 0.0 : A_mv(X_, B_, RP, O_A, true);
-    if (!(SOCP_KO & 16)) gemv_G_r<true>(xq, S_, H_, DZ);
-#pragma unroll
-    for (int t = 0; t < NS; ++t)
-      if (64 * t + lane < k) zs = fma(zv[t], sv[t], zs);  // (explicit: every instantiation sums z's alike, socp_batch_solve_qp's res at P = 0 included)
-    if (SOCP_KO & 64) {
-      nd = np_ = gap = d2 + p2 + zs;
-    } else {
-      double r3[3] = {d2, p2, zs};  // the three whole-wave sums in one interleaved scan
-      dpp_scan<3>(r3, lane, 0, false);
-      nd = sqrt(readlane_d(r3[0], 63));
-      np_ = sqrt(readlane_d(r3[1], 63));
-      gap = readlane_d(r3[2], 63);
-    }
-  }
-
   // The matrix part of solve_kkt(::DenseSolver) (densesolver.jl:66-85), between
   // the cone ops: n0 = GWiWi*k2 + dx (+A'dy if sing); m0 = ALi*n0 - dy, taken as
   // A*(Li*n0) - dy; cy = S^-1 m0; m0 = sing ? dy - cy : -cy (init: -cy);
@@ -3766,27 +3753,13 @@ struct Small {
             done = true;
             break;
           }
-          bool dm;
-          if constexpr (!(SOCP_KO & (2 | 4096))) {  // residuals and compute_scaling interleaved
-            // (after the last iteration the scaling is computed too, and unused)
-            dm = resid_scaling(nd, np_, gap, ll, dm_aa);
-            STAMP(SP_RESID);
-            if (it >= a.maxit) {
-              done = true;
-              break;
-            }
-          } else {
-            if (SOCP_KO & 2) {
-              nd = np_ = gap = 1.0;
-            } else {
-              residuals(nd, np_, gap);
-            }
-            STAMP(SP_RESID);
-            if (it >= a.maxit) {
-              done = true;
-              break;
-            }
-            dm = scaling_op(ll, dm_aa, true);
+          // residuals and compute_scaling interleaved
+          // (after the last iteration the scaling is computed too, and unused)
+          const bool dm = resid_scaling<!(SOCP_KO & 2), !(SOCP_KO & 4096)>(nd, np_, gap, ll, dm_aa);
+          STAMP(SP_RESID);
+          if (it >= a.maxit) {
+            done = true;
+            break;
           }
           STAMP(SP_VOP);
           if (dm) {
@@ -3809,7 +3782,7 @@ struct Small {
           }
           // (rmul!(dx, -1) etc., solver.jl:124: the residuals and ds were stored negated)
           // (fused launches: resid_scaling's G x pass has left this scaling's U in LDS)
-          fac_kind = (!(SOCP_KO & (2 | 4 | 4096)) && a.fuse_u) ? FAC_SCALED_U : FAC_SCALED;
+          fac_kind = (!(SOCP_KO & (2 | 4 | 16 | 4096)) && a.fuse_u) ? FAC_SCALED_U : FAC_SCALED;
           fac_aa = sing;
           fret = MP_SOLVE_HEAD;
           ret = RET_AFFINE;

@@ -7,7 +7,12 @@ runtime); the config's batch is generated once on the device by the first
 library, then every library solves it (fixed-K, device pointers) in
 interleaved rounds.  Prints per library the median / min solver-kernel time
 (HIP events, socp_last_kernel_ms) and the largest relative difference of x
-from the first library's result."""
+from the first library's result.  AB_KKT=1 times the plugin entry instead:
+socp_batch_kkt_solve on the first library's iterate (s, z) after two
+iterations, right-hand side (c, b, h, s); cx, cy, cz, cs and the status are
+then what is compared (printed as "dcx"; no iteration count).  The first
+library so makes the entry's input itself; every library is then timed and
+compared on that same (s, z), which is all a bitwise A/B needs."""
 import ctypes as C
 import os
 import sys
@@ -38,6 +43,7 @@ for p in paths:
     L.socp_ctx_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
     L.socp_ctx_sync.argtypes = [vp]
     L.socp_batch_solve.argtypes = common + [vp] * 5 + [vp, C.POINTER(_lib.Params)] + [vp] * 4 + [vp, vp]
+    L.socp_batch_kkt_solve.argtypes = common + [vp] * 14 + [C.c_int32]
     L.socp_generate.argtypes = common + [C.c_uint64, C.c_int64] + [vp] * 5
     L.socp_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.socp_last_error.restype = C.c_char_p
@@ -64,12 +70,26 @@ for _ in libs:
     outs.append(dict(x=torch.empty(B * n, **f64), y=torch.empty(B * max(m, 1), **f64), z=torch.empty(B * k, **f64),
                      s=torch.empty(B * k, **f64), it=torch.empty(B, dtype=torch.int32, device=dev),
                      st=torch.empty(B, dtype=torch.int32, device=dev)))
+KKT = os.environ.get("AB_KKT") == "1"  # AB_KKT=1: the plugin entry on an interior iterate
+keys = ("x", "y", "z", "s", "st") if KKT else ("x", "y", "z", "s", "it", "st")  # KKT: x, y, z, s hold cx, cy, cz, cs
+if KKT:
+    p2 = _lib.default_params(maxit=2, tol=0.0, flags=_lib.F_DEVICE_PTRS)
+    o = outs[0]
+    assert L0.socp_batch_solve(h0, C.byref(dims), kind, offs, dim, *map(P0, (c, A, b, G, h)), P0(sing), C.byref(p2),
+                               *map(P0, (o["x"], o["y"], o["z"], o["s"], o["it"], o["st"]))) == 0
+    L0.socp_ctx_sync(h0)
+    si, zi = o["s"].clone(), o["z"].clone()
 times = [[] for _ in libs]
 for r in range(reps + 1):
     for i, (p, L, hh) in enumerate(libs):
         o = outs[i]
-        rc = L.socp_batch_solve(hh, C.byref(dims), kind, offs, dim, *map(P0, (c, A, b, G, h)), P0(sing),
-                                C.byref(params), *map(P0, (o["x"], o["y"], o["z"], o["s"], o["it"], o["st"])))
+        if KKT:
+            rc = L.socp_batch_kkt_solve(hh, C.byref(dims), kind, offs, dim, P0(A), P0(G), P0(sing), P0(si), P0(zi),
+                                        *map(P0, (c, b, h, si, o["x"], o["y"], o["z"], o["s"], o["st"])),
+                                        _lib.F_DEVICE_PTRS | XI)
+        else:
+            rc = L.socp_batch_solve(hh, C.byref(dims), kind, offs, dim, *map(P0, (c, A, b, G, h)), P0(sing),
+                                    C.byref(params), *map(P0, (o["x"], o["y"], o["z"], o["s"], o["it"], o["st"])))
         if rc:
             raise RuntimeError(f"{p}: {rc} {L.socp_last_error().decode()}")
         L.socp_ctx_sync(hh)
@@ -84,8 +104,8 @@ for i, (p, _, _) in enumerate(libs):
     rel = ((x - x0).norm(dim=1) / x0.norm(dim=1).clamp_min(1e-300)).max().item()
     st = torch.bincount(outs[i]["st"].long(), minlength=5).tolist()
     # every output against the first library's, bit for bit (NaNs of failed problems included)
-    diff = [key for key in ("x", "y", "z", "s", "it", "st")
+    diff = [key for key in keys
             if not (key == "y" and m == 0) and not torch.equal(outs[i][key].view(torch.uint8), outs[0][key].view(torch.uint8))]
-    print(f"{sys.argv[1]} {os.path.relpath(p)}: median {t[len(t)//2]:.3f} ms  min {t[0]:.3f} ms  "
-          f"max rel dx vs first {rel:.2e}  bitwise {'equal' if not diff else 'DIFFERS in ' + ','.join(diff)}  "
-          f"status {st}  iters {int(outs[i]['it'].sum())}", flush=True)
+    print(f"{sys.argv[1]}{' kkt entry' if KKT else ''} {os.path.relpath(p)}: median {t[len(t)//2]:.3f} ms  min {t[0]:.3f} ms  "
+          f"max rel {'dcx' if KKT else 'dx'} vs first {rel:.2e}  bitwise {'equal' if not diff else 'DIFFERS in ' + ','.join(diff)}  "
+          f"status {st}" + ("" if KKT else f"  iters {int(outs[i]['it'].sum())}"), flush=True)
