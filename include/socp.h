@@ -603,6 +603,22 @@ int socp_debug_set_stamps(unsigned long long* dev_buf);
 int socp_debug_slot_plan(const socp_dims* dims, const int32_t* kind, const int32_t* offs,
                          const int32_t* dim, int32_t* rot, int32_t* kind0, int32_t* kind1);
 
+/* Testing hook (host only, no device work): does socp_batch_solve with these
+ * dims, this cone table (checked as a solve checks it) and these socp_params
+ * flags run an exact-fit kernel -- the pure-slot plain solver compiled for one
+ * launch geometry, dims, cone layout and slot plan as constants?  *exact = 1
+ * only when the plain solver runs (neither SOCP_F_EXPLICIT_INVERSE nor
+ * SOCP_F_DETECT_INFEASIBLE; warm starts and shared matrices do not matter),
+ * the slot plan chose a pure pair, n, m and k fill the compiled variant
+ * exactly, the cone table is the one the kernel holds, the SYRK's cone rows
+ * are fused (`sing` may be given or left to the device).  The one geometry compiled
+ * is n = 64, m = 16, k = 96 with POC(0, 32), SOC(32, 32), SOC(64, 32).
+ * SOCP_EXACT_FIT=0, SOCP_FUSE_U=0 or SOCP_SLOT_SPECIALISE=0 in the environment
+ * (read at every launch and by this call) give 0: the generic kernel runs, and
+ * the results are the same bits. */
+int socp_debug_exact_fit(const socp_dims* dims, const int32_t* kind, const int32_t* offs,
+                         const int32_t* dim, int32_t flags, int32_t* exact);
+
 #ifdef __cplusplus
 }
 #endif

@@ -300,6 +300,8 @@ static int cone_rows_uniform(const ConeTable& t, int nc) {
 // as before the residuals' G x pass learnt to form them
 // SOCP_INIT_OVERLAP: the initial point's G'G is formed by form_H's row loop on every kernel,
 // not under G's load in load_problem
+// SOCP_EXACT_FIT: a launch that fills its variant exactly runs the pair's generic pure-slot
+// kernel, not the one compiled for its geometry (small_exact_pair)
 static bool env_enabled(const char* name) {
   const char* e = getenv(name);
   return !(e && e[0] == '0' && e[1] == '\0');
@@ -322,7 +324,8 @@ extern "C" int socp_debug_slot_plan(const socp_dims* d, const int32_t* kind, con
   return 0;
 }
 
-int host::launch_small(socp_ctx* ctx, SmallArgs& args, const SmallVariant* v, bool qp) {
+// al_rows and fuse_u of a launch of variant v (args.cones, args.nc set)
+static void small_cone_geometry(SmallArgs& args, const SmallVariant* v) {
   args.al_rows = cone_rows_uniform(args.cones, args.nc);
   // (cones of 32 or 64 rows on a variant of whole 8-row-step chunks: a G x chunk lies in one cone)
   args.fuse_u = 0;
@@ -331,6 +334,47 @@ int host::launch_small(socp_ctx* ctx, SmallArgs& args, const SmallVariant* v, bo
     for (int c = 0; c < args.nc && c < NCS; ++c)
       if (args.cones.kind[c] == SOC_K) args.fuse_u |= 1 << c;
   }
+}
+
+// The pure-slot pair (SLOT_PAIR_*) whose exact-fit kernel this plain solve takes, or
+// SLOT_PAIR_NONE: the slot plan chose a pair, variant v has that pair's exact-fit kernel, and
+// dims, cone table, al_rows, slot_rot and fuse_u are the ones it was compiled for
+// (small_exact_fit: SOCP_FUSE_U=0 or SOCP_SLOT_SPECIALISE=0 so leave none).
+// args: cones, nc, n, m, k, al_rows, fuse_u, slot_rot, slot_kinds set.
+static int small_exact_pair(const SmallArgs& args, const SmallVariant* v) {
+  const int pair = slot_pair_of(args.slot_kinds & 15, args.slot_kinds >> 4);
+  if (pair == SLOT_PAIR_NONE || !v->exact_kernel[pair - 1] || !env_enabled("SOCP_EXACT_FIT")) return SLOT_PAIR_NONE;
+  return small_exact_fit(args, v->NQ, v->NP, v->MQ, pair) ? pair : SLOT_PAIR_NONE;
+}
+
+extern "C" int socp_debug_exact_fit(const socp_dims* d, const int32_t* kind, const int32_t* offs, const int32_t* dim,
+                                    int32_t flags, int32_t* exact) {
+  ConeTable tab;
+  int deg = 0;
+  if (!exact) return fail(SOCP_E_INVALID, "output pointer is NULL");
+  {
+    const int rc = check_problem(d, kind, offs, dim, &tab, &deg);
+    if (rc) return rc;
+  }
+  *exact = 0;
+  const SmallVariant* v = pick_variant(d->n, d->m, d->k);
+  if (!v || d->ncones > NCS || (flags & SOCP_F_FORCE_LARGE)) return 0;  // the blocked kernel's
+  // (the xi and di solvers keep their one kernel; the rest is what launch_small sets for a plain solve)
+  if (flags & (SOCP_F_EXPLICIT_INVERSE | SOCP_F_DETECT_INFEASIBLE)) return 0;
+  SmallArgs a{};
+  a.n = d->n;
+  a.m = d->m;
+  a.k = d->k;
+  a.nc = tab.nc;
+  a.cones = tab;
+  small_cone_geometry(a, v);
+  small_slot_plan(a.cones, a.nc, a.k, a.al_rows, env_enabled("SOCP_SLOT_SPECIALISE"), a.slot_rot, a.slot_kinds);
+  *exact = small_exact_pair(a, v) != SLOT_PAIR_NONE ? 1 : 0;
+  return 0;
+}
+
+int host::launch_small(socp_ctx* ctx, SmallArgs& args, const SmallVariant* v, bool qp) {
+  small_cone_geometry(args, v);
   size_t lds = small_lds_bytes(v->NQ, v->NP, v->MQ);
   if (lds > 160 * 1024) return fail(SOCP_E_UNSUPPORTED, "LDS footprint too large");
   const bool solver = args.mode == MODE_SOLVE;
@@ -353,6 +397,9 @@ int host::launch_small(socp_ctx* ctx, SmallArgs& args, const SmallVariant* v, bo
       kern = v->slot_kernel[pair - 1];
       args.slot_rot = rot;
       args.slot_kinds = kinds;
+      // the same solver compiled for exactly this launch's geometry, where there is one
+      const int ex = small_exact_pair(args, v);
+      if (ex != SLOT_PAIR_NONE) kern = v->exact_kernel[ex - 1];
     }
   }
   if (!kern) return fail(SOCP_E_UNSUPPORTED, "no compiled kernel for these flags");

@@ -32,6 +32,9 @@ struct SmallVariant {
   // socp_batch_solve_qp (KM 8): the solver with the quadratic term P, mixed slots
   const void* qp_kernel;
   const char* qp_name;
+  // the pair's plain solver compiled for one exact launch geometry (KM = (pair << 4) | KM_EXACT,
+  // socp_small.hpp ExactFit; gen_inst.py EXACT), else NULL: [SLOT_PAIR_* - 1]
+  const void* exact_kernel[4];
 };
 
 // table of compiled register-resident variants, ordered by (NQ, NP, MQ)

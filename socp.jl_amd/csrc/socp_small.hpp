@@ -161,6 +161,46 @@ inline void small_slot_plan(const ConeTable& t, int nc, int k, int al_rows, bool
   }
 }
 
+// Exact-fit solver kernels: socp_small_kernel<.., KM = (pair << 4) | KM_EXACT>,
+// the pure-slot plain solver compiled for ONE launch geometry.  The launch fills
+// its variant exactly (n = 16 NQ, k = 4 NP, m = 16 MQ), so the dims are
+// constants and every bounds predicate folds; al_rows, slot_rot and fuse_u are
+// constants too, and with them the cone table: k / (16 al_rows) cones of
+// 16 al_rows rows each, laid end to end, cone c SOC exactly when bit c of
+// fuse_u is set.  The phase loop is the generic kernel's, the G'G probe and the
+// KKT entry phase included (leaving them out gained nothing measurable,
+// DESIGN.md 5l).  One line per compiled kernel;
+// gen_inst.py's EXACT names the same (variant, pair) entries, and the host
+// takes the kernel only where small_exact_fit() says the launch is this one.
+struct ExactFit {
+  int NQ, NP, MQ, pair;
+  int al_rows, slot_rot, fuse_u;
+};
+constexpr int KM_EXACT = 128;
+constexpr ExactFit kExactFit[] = {
+    {4, 24, 1, SLOT_PAIR_SP, 2, 64, 0x100 | 2 | 4},  // n=64 m=16 k=96, POC32+SOC32+SOC32 (bench.py's C2)
+};
+constexpr int kExactFitCount = (int)(sizeof(kExactFit) / sizeof(kExactFit[0]));
+constexpr int exact_fit_index(int NQ, int NP, int MQ, int pair) {
+  for (int i = 0; i < kExactFitCount; ++i)
+    if (kExactFit[i].NQ == NQ && kExactFit[i].NP == NP && kExactFit[i].MQ == MQ && kExactFit[i].pair == pair) return i;
+  return -1;
+}
+// Is this launch the one the exact-fit kernel of (variant, pair) was compiled
+// for?  All of it is read from what launch_small has set in `a`.
+inline bool small_exact_fit(const SmallArgs& a, int NQ, int NP, int MQ, int pair) {
+  const int i = exact_fit_index(NQ, NP, MQ, pair);
+  if (i < 0) return false;
+  const ExactFit& e = kExactFit[i];
+  if (a.n != 16 * NQ || a.k != 4 * NP || a.m != 16 * MQ) return false;
+  if (a.al_rows != e.al_rows || a.slot_rot != e.slot_rot || a.fuse_u != e.fuse_u) return false;
+  const int d = 16 * e.al_rows;
+  if (a.nc * d != a.k) return false;
+  for (int c = 0; c < a.nc; ++c)
+    if (a.cones.offs[c] != c * d || a.cones.dim[c] != d) return false;
+  return true;
+}
+
 // MODE_SOLVE reads no right-hand side: with F_DETECT the slot of dx carries
 // the bits of the infeasibility tolerance, so that the layout of the kernel
 // arguments -- and with it the code of every kernel that does not detect --
@@ -926,12 +966,37 @@ __device__ __forceinline__ void factor_tile(d4 Dt, d4& W, bool& ok, const H& hoo
 // QP: the objective is x'Px/2 + c'x (socp_batch_solve_qp): H = P + G'W^-2 G
 // (+A'A) and rd = Px + A'y + G'z + c; P is streamed from global memory (add_P,
 // P_mv), never resident.
-template <int NQ, int NP, int MQ, bool XI = false, int KS0 = SLOT_MIXED, int KS1 = SLOT_MIXED, bool QP = false>
+// EX (KM_EXACT): the exact-fit kernel of kExactFit's (variant, pair) entry:
+// n, m, k, nc, al_rows, slot_rot and fuse_u are that entry's constants, not
+// the launch's arguments (ExactFit above).  Same operations in the same order:
+// only predicates that are always true at this geometry, and code this launch
+// never runs, go away.
+template <int NQ, int NP, int MQ, bool XI = false, int KS0 = SLOT_MIXED, int KS1 = SLOT_MIXED, bool QP = false,
+          bool EX = false>
 struct Small {
   using SH = Shape<NQ, NP, MQ>;
   static_assert((KS0 == SLOT_MIXED) == (KS1 == SLOT_MIXED), "both slots pure or both mixed");
   static_assert(KS0 == SLOT_MIXED || 4 * NP > 64, "pure slots: two-slot shapes only");
   static constexpr bool SLK = KS0 != SLOT_MIXED;
+  static constexpr int EXI = EX ? exact_fit_index(NQ, NP, MQ, slot_pair_of(KS0, KS1)) : -1;
+  static_assert(!EX || (EXI >= 0 && !XI && !QP), "exact fit: a kExactFit entry, plain solver");
+  static constexpr ExactFit EXF = kExactFit[EXI >= 0 ? EXI : 0];
+  static_assert(!EX || ((EXF.al_rows == 2 || EXF.al_rows == 4) && (EXF.fuse_u & 0x100) && NP % 8 == 0 &&
+                        (4 * NP) % (16 * EXF.al_rows) == 0),
+                "exact fit: fused U, whole cones of 32 or 64 rows");
+  // the launch's geometry: kernel arguments, or the exact-fit kernel's constants
+  __device__ __forceinline__ int al_rows() const {
+    if constexpr (EX) return EXF.al_rows;
+    else return a.al_rows;
+  }
+  __device__ __forceinline__ int slot_rot() const {
+    if constexpr (EX) return EXF.slot_rot;
+    else return a.slot_rot;
+  }
+  __device__ __forceinline__ int fuse_u() const {
+    if constexpr (EX) return EXF.fuse_u;
+    else return a.fuse_u;
+  }
   // which algebra a slot of kind KD can need
   static constexpr bool may_soc(int KD) { return KD != SLOT_POC; }
   static constexpr bool may_poc(int KD) { return KD != SLOT_SOC; }
@@ -990,7 +1055,8 @@ struct Small {
 
   __device__ __forceinline__ Small(const SmallArgs& args)
       : a(args), lane(threadIdx.x), g(threadIdx.x >> 4), cl(threadIdx.x & 15),
-        n(args.n), m(args.m), k(args.k), nc(args.nc) {}
+        n(EX ? 16 * NQ : args.n), m(EX ? 16 * MQ : args.m), k(EX ? 4 * NP : args.k),
+        nc(EX ? 4 * NP / (16 * EXF.al_rows) : args.nc) {}
 
 #ifndef SOCP_KO
 #define SOCP_KO 0  // timing knock-outs (tuning builds only; results are wrong): 1 G loaded once per wave,
@@ -1013,7 +1079,7 @@ struct Small {
   // 64 s + ln >= k hold no element (their index is only read from).
   __device__ __forceinline__ int el(int s, int ln) const {
     if constexpr (SLK) {
-      const int base = a.slot_rot ? (s ? 0 : k - 64) : 64 * s;  // wave-uniform
+      const int base = slot_rot() ? (s ? 0 : k - 64) : 64 * s;  // wave-uniform
       return base + ln;
     } else {
       return 64 * s + ln;
@@ -1065,7 +1131,7 @@ struct Small {
       // the cone's lanes: from its first position in the slots, eo_ rotated
       int o = eo_;
       if constexpr (SLK) {
-        const int rot = a.slot_rot;  // 0 or 64
+        const int rot = slot_rot();  // 0 or 64
         o = eo_ + rot >= k && rot ? eo_ + rot - k : eo_ + rot;
       }
       const int st = o > 64 * s ? o : 64 * s;
@@ -1360,8 +1426,8 @@ struct Small {
     MARK_BEGIN("cone_reduce");
     LANE_IDS();
     constexpr int NS = KP > 64 ? 2 : 1;  // slots that can hold elements of this shape
-    if (a.al_rows) {  // row-aligned cones: registers only
-      const int R = a.al_rows;
+    if (al_rows()) {  // row-aligned cones: registers only
+      const int R = al_rows();
       constexpr int NL = live_count(L0, L1, NS, NV);
       constexpr unsigned MXM = live_mx(MX, L0, L1, NS, NV);
       if constexpr (NL > 0) {
@@ -1438,8 +1504,8 @@ struct Small {
     LANE_IDS();
     constexpr int NS = KP > 64 ? 2 : 1;
     const int rl = lane & 15;
-    if (a.al_rows) {  // row-aligned cones: every lane of the cone gets its total
-      const int R = a.al_rows;
+    if (al_rows()) {  // row-aligned cones: every lane of the cone gets its total
+      const int R = al_rows();
       constexpr int NL = live_count(L0, L1, NS, NV);
       if constexpr (NL > 0) {
         double w[NL];
@@ -1879,7 +1945,7 @@ struct Small {
       // the U parts behind branches inside one shared instance those launches
       // lost 0.2-0.6 ms at C2's shape.
       if constexpr (RESID && !(SOCP_KO & 16)) {
-        if (__builtin_expect(SCAL && !(SOCP_KO & 4) && a.fuse_u, 0))
+        if (__builtin_expect(SCAL && !(SOCP_KO & 4) && fuse_u(), 0))
           gemv_G_r<true, true>(xq, S_, H_, DZ);
         else
           gemv_G_r<true>(xq, S_, H_, DZ);
@@ -2351,7 +2417,10 @@ struct Small {
       const int row = 4 * pp + g_;
       c.ca = LDS(CA + row);
       c.cb = LDS(CBV + row);
-      c.ub = ubt(row) + cl_;  // O_U + cone(row) * NPAD
+      if constexpr (EX)
+        c.ub = O_U + (pp / (4 * EXF.al_rows)) * NPAD + cl_;  // a row step lies in one cone
+      else
+        c.ub = ubt(row) + cl_;  // O_U + cone(row) * NPAD
     } else {
       LANE_IDS();
       const int row = 4 * pp + g;
@@ -3148,10 +3217,10 @@ struct Small {
     bool usoc = false;  // wave-uniform: the chunk's cone is SOC
     int ucone = 0, upos = 0, ulast = 0;
     if constexpr (FU && CH == 8) {
-      ulast = a.al_rows == 4;  // a cone is two chunks (64 rows) or one (32)
+      ulast = al_rows() == 4;  // a cone is two chunks (64 rows) or one (32)
       ucone = (P0 / 8) >> ulast;
       upos = (P0 / 8) & ulast;  // the chunk's place in its cone
-      usoc = (a.fuse_u >> ucone) & 1;
+      usoc = (fuse_u() >> ucone) & 1;
       if (usoc) {
 #pragma unroll
         for (int j = 0; j < CH; ++j) uw[j] = LDS(WB + 4 * (P0 + j) + g);
@@ -3782,7 +3851,7 @@ struct Small {
           }
           // (rmul!(dx, -1) etc., solver.jl:124: the residuals and ds were stored negated)
           // (fused launches: resid_scaling's G x pass has left this scaling's U in LDS)
-          fac_kind = (!(SOCP_KO & (2 | 4 | 16 | 4096)) && a.fuse_u) ? FAC_SCALED_U : FAC_SCALED;
+          fac_kind = (!(SOCP_KO & (2 | 4 | 16 | 4096)) && fuse_u()) ? FAC_SCALED_U : FAC_SCALED;
           fac_aa = sing;
           fret = MP_SOLVE_HEAD;
           ret = RET_AFFINE;
@@ -3952,13 +4021,16 @@ struct Small {
 // KM bit 0: the plugin-entry kernel (MODE_KKT / MODE_SETUP / MODE_SOLVEKKT)
 // instead of the solver; bit 1: the explicit-inverse variant (XI above);
 // bit 2 (KM = 4): the solver with SOCP_F_DETECT_INFEASIBLE;
-// bit 3 (KM = 8): the QP solver (socp_batch_solve_qp), mixed slots only
+// bit 3 (KM = 8): the QP solver (socp_batch_solve_qp), mixed slots only;
+// bit 7 (KM_EXACT, with a pair): the pair's plain solver at one exact launch geometry (ExactFit)
 template <int NQ, int NP, int MQ, int KM>
 #ifndef SOCP_DEV_MINW
 #define SOCP_DEV_MINW 1  // probe builds only: waves per SIMD the register allocation must allow
 #endif
 __global__ void __launch_bounds__(64, (KM & 3) == 0 ? SOCP_DEV_MINW : 1) socp_small_kernel(SmallArgs args) {
-  Small<NQ, NP, MQ, (KM & 2) != 0, slot_pair_kind(KM >> 4, 0), slot_pair_kind(KM >> 4, 1), (KM & 8) != 0> S(args);
+  Small<NQ, NP, MQ, (KM & 2) != 0, slot_pair_kind((KM >> 4) & 7, 0), slot_pair_kind((KM >> 4) & 7, 1), (KM & 8) != 0,
+        (KM & KM_EXACT) != 0>
+      S(args);
   S.init_tables();
   STAMP_START_S(S);
   while (true) {

@@ -108,6 +108,20 @@ def slot_plan(cones, k):
     return rot.value, k0.value, k1.value
 
 
+def exact_fit(cones, n, m, k, *, flags=0):
+    """socp_debug_exact_fit: whether a batch_solve of these dims, this cone
+    table and these socp_params flags (``_lib.F_*``) runs the solver kernel
+    compiled for exactly that launch geometry.  Host only."""
+    kind, offs, dim = cone_arrays(cones)
+    d = _lib.Dims(1, int(n), int(m), int(k), len(kind))
+    ex = C.c_int32()
+    rc = _lib.load().socp_debug_exact_fit(C.byref(d), kind.ctypes.data, offs.ctypes.data, dim.ctypes.data,
+                                          int(flags), C.byref(ex))
+    if rc:
+        raise SocpError(rc, _lib.load().socp_last_error().decode())
+    return bool(ex.value)
+
+
 # --------------------------------------------------------------- batched
 def _is_torch(a):
     return a is not None and not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")

@@ -39,6 +39,7 @@ EXPORTED = [
     "socp_sqr_scaling", "socp_sqr_h2d_bytes", "socp_sqr_record_bytes", "socp_sqr_destroy",
     "socp_sqr_solve_socp", "socp_ctx_set_infeasibility_tol", "socp_debug_slot_plan",
     "socp_batch_solve_qp", "socp_batch_equilibrate", "socp_ctx_set_equilibration_passes",
+    "socp_debug_exact_fit",
 ]
 
 OUTCOME_BYTES = 32  # sizeof(socp_outcome): int32 status, int32 iters, double rd, rp, gap
@@ -109,6 +110,8 @@ def load():
     L.socp_supported.argtypes = [C.POINTER(Dims)]
     if hasattr(L, "socp_debug_slot_plan"):  # (absent from older A/B builds)
         L.socp_debug_slot_plan.argtypes = [C.POINTER(Dims), i32p, i32p, i32p] + [C.POINTER(C.c_int32)] * 3
+    if hasattr(L, "socp_debug_exact_fit"):  # (absent from older A/B builds)
+        L.socp_debug_exact_fit.argtypes = [C.POINTER(Dims), i32p, i32p, i32p, C.c_int32, C.POINTER(C.c_int32)]
     common = [vp, C.POINTER(Dims), i32p, i32p, i32p]
     L.socp_batch_solve.argtypes = common + [dp] * 5 + [u8p, C.POINTER(Params)] + [dp] * 4 + [i32p, i32p]
     L.socp_batch_solve_ex.argtypes = common + [dp] * 5 + [u8p, C.POINTER(Params)] + [dp] * 4 + [i32p, i32p, dp]
