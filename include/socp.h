@@ -326,6 +326,30 @@ int socp_batch_kkt_solve(socp_ctx* ctx, const socp_dims* dims,
                          double* cx, double* cy, double* cz, double* cs,
                          int32_t* kkt_status, int32_t flags);  /* flags: SOCP_F_DEVICE_PTRS | SOCP_F_FORCE_LARGE | SOCP_F_SHARED_MATRICES */
 
+/* socp_batch_kkt_solve for a quadratic objective (socp_batch_solve_qp's P: per
+ * problem n x n column-major, ONE matrix with SOCP_F_SHARED_MATRICES; symmetric
+ * positive semidefinite, unchecked).  The first row of the block system
+ * becomes
+ *     P cx + A'cy + G'cz = dx
+ * and the other three stay (A cx = dy, G cx + cs = dz, lam o (W cz + W^-T cs)
+ * = ds): the reduced matrix is H = P + G'W^-2 G (+A'A when sing) and nothing
+ * else of solve_kkt changes.  A P that leaves H indefinite gives that problem
+ * alone SOCP_CHOL_H_FAILED and a NaN solution (what socp_dense_solve_kkt
+ * returns after a failed setup_iter).  The sing == NULL probe factors G'G
+ * without P, as the solver's does.
+ * P == NULL runs exactly what socp_batch_kkt_solve runs (the same kernel, the
+ * same bits).  flags: SOCP_F_DEVICE_PTRS | SOCP_F_FORCE_LARGE |
+ * SOCP_F_SHARED_MATRICES; with a P, SOCP_F_EXPLICIT_INVERSE returns
+ * SOCP_E_UNSUPPORTED (no QP kernel is compiled in that order, as for the
+ * solver) and socp_last_error names this entry. */
+int socp_batch_kkt_solve_qp(socp_ctx* ctx, const socp_dims* dims,
+                            const int32_t* cone_kind, const int32_t* cone_offs, const int32_t* cone_dim,
+                            const double* P, const double* A, const double* G, const uint8_t* sing,
+                            const double* s, const double* z,
+                            const double* dx, const double* dy, const double* dz, const double* ds,
+                            double* cx, double* cy, double* cz, double* cs,
+                            int32_t* kkt_status, int32_t flags);
+
 /* The same two methods split the way the reference's KKTSolver plugin is
  * (densesolver.jl): a handle stands for a batch of DenseSolver objects.
  *   socp_dense_create      replaces DenseSolver(...) construction
@@ -362,12 +386,26 @@ int socp_batch_kkt_solve(socp_ctx* ctx, const socp_dims* dims,
  * per problem host-to-device and each solve_kkt n+m+2k; A and G move once, at
  * create (socp_dense_h2d_bytes reports the last call's count).  The results are
  * bitwise those of socp_batch_kkt_solve on the same inputs.  Device memory:
- * socp_dense_record_bytes() per problem plus A, G. */
+ * socp_dense_record_bytes() per problem plus A, G.
+ *   socp_dense_create_qp   the same handle for a quadratic objective: P (as in
+ *                          socp_batch_kkt_solve_qp) is copied into the handle
+ *                          beside A and G and counted by socp_dense_h2d_bytes at
+ *                          create; setup_iter factors H = P + G'W^-2 G (+A'A)
+ *                          (where the record holds Li it is the inverse of that
+ *                          H), solve_kkt reads the record alone.  Results are
+ *                          bitwise those of socp_batch_kkt_solve_qp.  P == NULL
+ *                          is socp_dense_create; with a P,
+ *                          SOCP_F_EXPLICIT_INVERSE returns SOCP_E_UNSUPPORTED
+ *                          and socp_last_error names this entry. */
 typedef struct socp_dense socp_dense;
 int socp_dense_create(socp_ctx* ctx, const socp_dims* dims,
                       const int32_t* cone_kind, const int32_t* cone_offs, const int32_t* cone_dim,
                       const double* A, const double* G, const uint8_t* sing, int32_t flags,
                       socp_dense** out);
+int socp_dense_create_qp(socp_ctx* ctx, const socp_dims* dims,
+                         const int32_t* cone_kind, const int32_t* cone_offs, const int32_t* cone_dim,
+                         const double* P, const double* A, const double* G, const uint8_t* sing,
+                         int32_t flags, socp_dense** out);
 int socp_dense_setup_iter(socp_dense* h, const double* s, const double* z, int32_t* status);
 int socp_dense_solve_kkt(socp_dense* h, const double* dx, const double* dy, const double* dz,
                          const double* ds, double* cx, double* cy, double* cz, double* cs,
@@ -506,7 +544,27 @@ int socp_pack_csc(socp_ctx* ctx, int64_t batch, int32_t rows, int32_t cols,
  *   socp_ingest_submit then requires A, G and sing to be NULL and
  *       set_matrices to have been called (SOCP_E_INVALID otherwise);
  *       socp_ingest_next_inputs hands back NULL for A, G and sing;
- *       socp_ingest_submit_csc returns SOCP_E_INVALID. */
+ *       socp_ingest_submit_csc returns SOCP_E_INVALID.
+ * Quadratic objectives (socp_batch_solve_qp's P; dense only, no CSC form):
+ *   socp_ingest_submit_qp(ing, B, P, c, A, b, G, h, sing, params, &ticket):
+ *       socp_ingest_submit with the batch's B matrices P; results are bitwise
+ *       those of socp_batch_solve_qp on the same inputs.  The slots' pinned
+ *       and device room for P is allocated by the first call that brings a P
+ *       (this one or socp_ingest_next_P); that call may synchronise the
+ *       device once.  P == NULL is socp_ingest_submit, and so is any later
+ *       plain submit: the linear solve, bit for bit.  With a P,
+ *       SOCP_F_EXPLICIT_INVERSE or SOCP_F_DETECT_INFEASIBLE in params->flags
+ *       returns SOCP_E_UNSUPPORTED before the slot is claimed, as the
+ *       synchronous entry refuses them.
+ *   socp_ingest_next_P(ing, &P): the next slot's pinned P block (max_batch
+ *       matrices), to be written in place like socp_ingest_next_inputs'
+ *       arrays; allocates as above.  SOCP_E_INVALID on a shared ingest.
+ *   socp_ingest_set_matrices_qp(ing, P, A, G, sing): socp_ingest_set_matrices
+ *       with the one n x n P of a SOCP_F_SHARED_MATRICES ingest (P == NULL:
+ *       none).  socp_ingest_submit_qp on such an ingest requires its own P to
+ *       be NULL and a set_matrices_qp that gave one (SOCP_E_INVALID
+ *       otherwise) and solves with it; socp_ingest_submit stays the linear
+ *       solve; plain socp_ingest_set_matrices clears the P. */
 typedef struct socp_ingest socp_ingest;
 int socp_ingest_create(socp_ctx* ctx, const socp_dims* dims,
                        const int32_t* cone_kind, const int32_t* cone_offs, const int32_t* cone_dim,
@@ -517,6 +575,12 @@ int socp_ingest_next_inputs(socp_ingest* ing, double** c, double** A, double** b
 int socp_ingest_submit(socp_ingest* ing, int64_t batch, const double* c, const double* A,
                        const double* b, const double* G, const double* h, const uint8_t* sing,
                        const socp_params* params, int64_t* ticket);
+int socp_ingest_submit_qp(socp_ingest* ing, int64_t batch, const double* P, const double* c,
+                          const double* A, const double* b, const double* G, const double* h,
+                          const uint8_t* sing, const socp_params* params, int64_t* ticket);
+int socp_ingest_set_matrices_qp(socp_ingest* ing, const double* P, const double* A, const double* G,
+                                const uint8_t* sing);
+int socp_ingest_next_P(socp_ingest* ing, double** P);
 int socp_ingest_submit_csc(socp_ingest* ing, int64_t batch, const double* c, const double* b,
                            const double* h, const uint8_t* sing,
                            const int64_t* A_nz_offs, const int64_t* A_colptr, const int64_t* A_rowval,

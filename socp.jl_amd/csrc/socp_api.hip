@@ -382,7 +382,8 @@ int host::launch_small(socp_ctx* ctx, SmallArgs& args, const SmallVariant* v, bo
   const bool xi = (args.flags & SOCP_F_EXPLICIT_INVERSE) != 0 && v->xi_kernel;
   // SOCP_F_DETECT_INFEASIBLE: the solver instantiation with the rule (never with xi: check_detect_flags)
   const bool di = solver && !xi && (args.flags & SOCP_F_DETECT_INFEASIBLE) != 0;
-  const void* kern = qp   ? v->qp_kernel
+  // qp: the QP solver, or (the plugin modes) the QP plugin-entry kernel
+  const void* kern = qp   ? (solver ? v->qp_kernel : v->qp_kkt_kernel)
                      : di ? v->di_kernel
                      : xi ? (solver ? v->xi_kernel : v->xi_kkt_kernel)
                           : (solver ? v->kernel : v->kkt_kernel);
@@ -421,7 +422,7 @@ int host::launch_small(socp_ctx* ctx, SmallArgs& args, const SmallVariant* v, bo
   HIPCHK(timing_begin(ctx));
   HIPCHK(hipLaunchKernel(kern, dim3((unsigned)blocks), dim3(64), kargs, lds, ctx->stream));
   HIPCHK(timing_end(ctx));
-  ctx->last_name = qp   ? v->qp_name
+  ctx->last_name = qp   ? (solver ? v->qp_name : v->qp_kkt_name)
                    : di ? v->di_name
                    : xi ? (solver ? v->xi_name : v->xi_kkt_name)
                         : (solver ? v->name : v->kkt_name);
@@ -848,14 +849,21 @@ extern "C" int socp_debug_set_kkt_dump(double* dev_buf) {
 #endif
 }
 
-extern "C" int socp_batch_kkt_solve(socp_ctx* ctx, const socp_dims* dims, const int32_t* cone_kind,
-                                    const int32_t* cone_offs, const int32_t* cone_dim,
-                                    const double* A, const double* G, const uint8_t* sing,
-                                    const double* s, const double* z, const double* dx,
-                                    const double* dy, const double* dz, const double* ds,
-                                    double* cx, double* cy, double* cz, double* cs,
-                                    int32_t* kkt_status, int32_t flags) {
+// socp_batch_kkt_solve, and with Pm != NULL socp_batch_kkt_solve_qp: the QP
+// plugin-entry kernels, whose first block row is P cx + A'cy + G'cz = dx
+static int batch_kkt_impl(socp_ctx* ctx, const socp_dims* dims, const int32_t* cone_kind,
+                          const int32_t* cone_offs, const int32_t* cone_dim, const double* Pm,
+                          const double* A, const double* G, const uint8_t* sing,
+                          const double* s, const double* z, const double* dx,
+                          const double* dy, const double* dz, const double* ds,
+                          double* cx, double* cy, double* cz, double* cs,
+                          int32_t* kkt_status, int32_t flags) {
   if (!ctx) return fail(SOCP_E_INVALID, "ctx is NULL");
+  const bool qp = Pm != nullptr;
+  if (qp && (flags & SOCP_F_EXPLICIT_INVERSE))
+    return fail(SOCP_E_UNSUPPORTED,
+                "socp_batch_kkt_solve_qp with SOCP_F_EXPLICIT_INVERSE: no QP kernel is compiled in the "
+                "explicit-inverse operation order");
   SmallArgs a;
   memset(&a, 0, sizeof(a));
   int degree = 0;
@@ -868,6 +876,7 @@ extern "C" int socp_batch_kkt_solve(socp_ctx* ctx, const socp_dims* dims, const 
     return fail(SOCP_E_INVALID, "NULL data pointer");
   const bool force_large = (flags & SOCP_F_FORCE_LARGE) != 0;
   const SmallVariant* v = (force_large || dims->ncones > NCS) ? nullptr : pick_variant(n, m, k);
+  if (qp && v && !v->qp_kkt_kernel) v = nullptr;  // no QP instantiation of the shape: the blocked kernel
   if (!v && !large_fits(n, m, k, dims->ncones, nullptr))
     return fail(SOCP_E_UNSUPPORTED, kUnsupported);
   HIPCHK(hipSetDevice(ctx->device));
@@ -883,6 +892,11 @@ extern "C" int socp_batch_kkt_solve(socp_ctx* ctx, const socp_dims* dims, const 
   TRY(st.in(X::B_A, A, MB * m * n, &a.A));
   TRY(st.in(X::B_G, G, MB * k * n, &a.G));
   TRY(st.in(X::B_SING, sing, MB, &a.sing));
+  if (qp) {
+    const double* Pd = nullptr;
+    TRY(st.in(X::B_P, Pm, MB * n * n, &Pd));
+    small_set_qp_plugin(a, Pd);
+  }
   TRY(st.out(X::B_S, const_cast<double*>(s), (size_t)B * k, true, &a.s));
   TRY(st.out(X::B_Z, const_cast<double*>(z), (size_t)B * k, true, &a.z));
   TRY(st.in(X::B_DX, dx, (size_t)B * n, &a.dx));
@@ -896,7 +910,7 @@ extern "C" int socp_batch_kkt_solve(socp_ctx* ctx, const socp_dims* dims, const 
   TRY(st.out(X::B_ST, kkt_status, (size_t)B, false, &a.status));
   TRY(st.reserve(X::B_CNT, 256));
   a.counter = (int32_t*)ctx->buf[X::B_CNT].p;
-  TRY(v ? launch_small(ctx, a, v) : launch_large(ctx, a));
+  TRY(v ? launch_small(ctx, a, v, qp) : launch_large(ctx, a, nullptr, qp));
   TRY(st.back(cx, a.cx, (size_t)B * n));
   TRY(st.back(cy, a.cy, (size_t)B * m));
   TRY(st.back(cz, a.cz, (size_t)B * k));
@@ -904,4 +918,26 @@ extern "C" int socp_batch_kkt_solve(socp_ctx* ctx, const socp_dims* dims, const 
   TRY(st.back(kkt_status, a.status, (size_t)B));
   if (!dev) HIPCHK(hipStreamSynchronize(ctx->stream));
   return 0;
+}
+
+extern "C" int socp_batch_kkt_solve(socp_ctx* ctx, const socp_dims* dims, const int32_t* cone_kind,
+                                    const int32_t* cone_offs, const int32_t* cone_dim,
+                                    const double* A, const double* G, const uint8_t* sing,
+                                    const double* s, const double* z, const double* dx,
+                                    const double* dy, const double* dz, const double* ds,
+                                    double* cx, double* cy, double* cz, double* cs,
+                                    int32_t* kkt_status, int32_t flags) {
+  return batch_kkt_impl(ctx, dims, cone_kind, cone_offs, cone_dim, nullptr, A, G, sing, s, z, dx, dy, dz, ds, cx, cy,
+                        cz, cs, kkt_status, flags);
+}
+
+extern "C" int socp_batch_kkt_solve_qp(socp_ctx* ctx, const socp_dims* dims, const int32_t* cone_kind,
+                                       const int32_t* cone_offs, const int32_t* cone_dim, const double* P,
+                                       const double* A, const double* G, const uint8_t* sing,
+                                       const double* s, const double* z, const double* dx,
+                                       const double* dy, const double* dz, const double* ds,
+                                       double* cx, double* cy, double* cz, double* cs,
+                                       int32_t* kkt_status, int32_t flags) {
+  return batch_kkt_impl(ctx, dims, cone_kind, cone_offs, cone_dim, P, A, G, sing, s, z, dx, dy, dz, ds, cx, cy, cz,
+                        cs, kkt_status, flags);
 }

@@ -17,19 +17,26 @@ struct socp_dense {
   SmallArgs a;  // problem part filled at create
   const SmallVariant* v = nullptr;
   int64_t rec_stride = 0;
+  bool qp = false;         // socp_dense_create_qp gave a P: the QP plugin-entry kernels
   bool ready = false;      // setup_iter has run
   int64_t h2d_bytes = 0;   // host-to-device bytes moved by the last call
-  enum { D_A, D_G, D_SING, D_ZERO, D_REC, D_S, D_Z, D_DX, D_DY, D_DZ, D_DS, D_CX, D_CY, D_CZ, D_CS,
+  enum { D_A, D_G, D_SING, D_P, D_ZERO, D_REC, D_S, D_Z, D_DX, D_DY, D_DZ, D_DS, D_CX, D_CY, D_CZ, D_CS,
          D_ST, D_CNT, ND };
   DevBuf buf[ND];
 };
 
-extern "C" int socp_dense_create(socp_ctx* ctx, const socp_dims* dims, const int32_t* cone_kind,
-                                 const int32_t* cone_offs, const int32_t* cone_dim, const double* A,
-                                 const double* G, const uint8_t* sing, int32_t flags, socp_dense** out) {
+// socp_dense_create, and with Pm != NULL socp_dense_create_qp: P is kept beside A and G
+static int dense_create_impl(socp_ctx* ctx, const socp_dims* dims, const int32_t* cone_kind,
+                             const int32_t* cone_offs, const int32_t* cone_dim, const double* Pm, const double* A,
+                             const double* G, const uint8_t* sing, int32_t flags, socp_dense** out) {
   if (!out) return fail(SOCP_E_INVALID, "out is NULL");
   *out = nullptr;
   if (!ctx) return fail(SOCP_E_INVALID, "ctx is NULL");
+  const bool qp = Pm != nullptr;
+  if (qp && (flags & SOCP_F_EXPLICIT_INVERSE))
+    return fail(SOCP_E_UNSUPPORTED,
+                "socp_dense_create_qp with SOCP_F_EXPLICIT_INVERSE: no QP kernel is compiled in the explicit-inverse "
+                "operation order");
   socp_dense* h = new socp_dense();
   h->ctx = ctx;
   SmallArgs& a = h->a;
@@ -46,6 +53,8 @@ extern "C" int socp_dense_create(socp_ctx* ctx, const socp_dims* dims, const int
   if (B > 0 && (!G || (m > 0 && !A))) return bail(fail(SOCP_E_INVALID, "NULL data pointer"));
   const bool force_large = (flags & SOCP_F_FORCE_LARGE) != 0;
   h->v = (force_large || dims->ncones > NCS) ? nullptr : pick_variant(n, m, k);
+  if (qp && h->v && !h->v->qp_kkt_kernel) h->v = nullptr;  // no QP instantiation of the shape: the blocked kernel
+  h->qp = qp;
   if (!h->v && !large_fits(n, m, k, dims->ncones, nullptr))
     return bail(fail(SOCP_E_UNSUPPORTED, kUnsupported));
   if (hipSetDevice(ctx->device) != hipSuccess) return bail(fail(SOCP_E_HIP, "hipSetDevice"));
@@ -63,6 +72,10 @@ extern "C" int socp_dense_create(socp_ctx* ctx, const socp_dims* dims, const int
   if ((rc = st.own(D::D_A, A, MB * m * n * sizeof(double)))) return bail(rc);
   if ((rc = st.own(D::D_G, G, MB * k * n * sizeof(double)))) return bail(rc);
   if ((rc = st.own(D::D_SING, sing, MB))) return bail(rc);
+  if (qp) {
+    if ((rc = st.own(D::D_P, Pm, MB * n * n * sizeof(double)))) return bail(rc);
+    small_set_qp_plugin(a, (const double*)h->buf[D::D_P].p);
+  }
   a.A = m > 0 ? (const double*)h->buf[D::D_A].p : nullptr;
   a.G = (const double*)h->buf[D::D_G].p;
   a.sing = sing ? (const uint8_t*)h->buf[D::D_SING].p : nullptr;
@@ -80,13 +93,26 @@ extern "C" int socp_dense_create(socp_ctx* ctx, const socp_dims* dims, const int
   return 0;
 }
 
+extern "C" int socp_dense_create(socp_ctx* ctx, const socp_dims* dims, const int32_t* cone_kind,
+                                 const int32_t* cone_offs, const int32_t* cone_dim, const double* A,
+                                 const double* G, const uint8_t* sing, int32_t flags, socp_dense** out) {
+  return dense_create_impl(ctx, dims, cone_kind, cone_offs, cone_dim, nullptr, A, G, sing, flags, out);
+}
+
+extern "C" int socp_dense_create_qp(socp_ctx* ctx, const socp_dims* dims, const int32_t* cone_kind,
+                                    const int32_t* cone_offs, const int32_t* cone_dim, const double* P,
+                                    const double* A, const double* G, const uint8_t* sing, int32_t flags,
+                                    socp_dense** out) {
+  return dense_create_impl(ctx, dims, cone_kind, cone_offs, cone_dim, P, A, G, sing, flags, out);
+}
+
 extern "C" int socp_dense_destroy(socp_dense* h) {
   handle_free(h);
   return 0;
 }
 
 static int dense_launch(socp_dense* h, SmallArgs& a) {
-  return h->v ? launch_small(h->ctx, a, h->v) : launch_large(h->ctx, a, a.rec);
+  return h->v ? launch_small(h->ctx, a, h->v, h->qp) : launch_large(h->ctx, a, a.rec, h->qp);
 }
 
 extern "C" int socp_dense_setup_iter(socp_dense* h, const double* s, const double* z, int32_t* status) {

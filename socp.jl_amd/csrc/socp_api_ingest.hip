@@ -26,6 +26,10 @@ struct IngestSlot {
   void* pin_csc = nullptr;  // CSC staging, grown on its own so pin_in never moves
   size_t pin_in_cap = 0, pin_out_cap = 0, pin_csc_cap = 0;
   DevBuf dev_in, dev_out, dev_csc;
+  // P (socp_ingest_submit_qp): blocks of their own, allocated by the first call that brings a P
+  // (ingest_ensure_P), so that pin_in and the pointers handed out for it never move
+  void* pin_P = nullptr;
+  DevBuf dev_P;
   hipEvent_t ready = nullptr, solved = nullptr, done = nullptr;
   int64_t ticket = -1;  // outstanding ticket, -1 when free
   int64_t batch = 0;
@@ -69,6 +73,10 @@ struct socp_ingest {
   // (socp_ingest_set_matrices), not in the slots
   bool shared = false, have_mat = false, mat_sing = false;
   DevBuf mat;
+  // the slots have their P blocks (a per-problem ingest); a shared ingest's one P
+  // (socp_ingest_set_matrices_qp) lives in mat_P, mat_qp while it holds one
+  bool have_P = false, mat_qp = false;
+  DevBuf mat_P;
 };
 
 // the byte layout of one slot's blocks for `B` problems
@@ -117,6 +125,8 @@ static void ingest_free(socp_ingest* g) {
     if (sl.pin_in) (void)hipHostFree(sl.pin_in);
     if (sl.pin_out) (void)hipHostFree(sl.pin_out);
     if (sl.pin_csc) (void)hipHostFree(sl.pin_csc);
+    if (sl.pin_P) (void)hipHostFree(sl.pin_P);
+    sl.dev_P.release();
     sl.dev_in.release();
     sl.dev_out.release();
     sl.dev_csc.release();
@@ -127,6 +137,7 @@ static void ingest_free(socp_ingest* g) {
   g->counter.release();
   g->err.release();
   g->mat.release();
+  g->mat_P.release();
   if (g->h2d) (void)hipStreamDestroy(g->h2d);
   if (g->d2h) (void)hipStreamDestroy(g->d2h);
   delete g;
@@ -203,10 +214,43 @@ extern "C" int socp_ingest_next_inputs(socp_ingest* g, double** c, double** A, d
   return 0;
 }
 
+// the slots' pinned and device room for max_batch matrices P, on the first call that brings one
+// (the allocations may synchronise the device once; blocks in flight are not touched)
+static int ingest_ensure_P(socp_ingest* g) {
+  if (g->have_P) return 0;
+  HIPCHK(hipSetDevice(g->ctx->device));
+  const size_t bytes = al_up(sizeof(double) * (size_t)g->dims.batch * g->dims.n * g->dims.n);
+  for (auto& sl : g->slot) {
+    if (!sl.pin_P && hipHostMalloc(&sl.pin_P, bytes, hipHostMallocDefault) != hipSuccess) {
+      sl.pin_P = nullptr;
+      return fail(SOCP_E_NOMEM, "pinned host allocation failed");
+    }
+    if (sl.dev_P.ensure(bytes)) return fail(SOCP_E_NOMEM, "device allocation failed");
+  }
+  g->have_P = true;
+  return 0;
+}
+
+// the pinned P block of the slot the next socp_ingest_submit_qp will use (socp_ingest_next_inputs' sibling)
+extern "C" int socp_ingest_next_P(socp_ingest* g, double** P) {
+  if (!g) return fail(SOCP_E_INVALID, "ingest is NULL");
+  if (!P) return fail(SOCP_E_INVALID, "P is NULL");
+  *P = nullptr;
+  if (g->shared)
+    return fail(SOCP_E_INVALID, "shared ingest: the slots stage no P (socp_ingest_set_matrices_qp gives it)");
+  IngestSlot& sl = g->slot[g->next & 1];
+  if (sl.ticket >= 0) return fail(SOCP_E_INVALID, "the next slot is busy: wait for its ticket first");
+  TRY(ingest_ensure_P(g));
+  *P = (double*)sl.pin_P;
+  return 0;
+}
+
 // SOCP_F_SHARED_MATRICES: the one A (m x n), G (k x n) and sing byte (NULL: the
-// device probe) of every later batch.  Host pointers, copied synchronously;
-// only with no ticket outstanding.
-extern "C" int socp_ingest_set_matrices(socp_ingest* g, const double* A, const double* G, const uint8_t* sing) {
+// device probe) of every later batch, and (socp_ingest_set_matrices_qp) their one
+// P (n x n; NULL: none, later batches are linear).  Host pointers, copied
+// synchronously; only with no ticket outstanding.
+static int ingest_set_matrices_impl(socp_ingest* g, const double* Pm, const double* A, const double* G,
+                                    const uint8_t* sing) {
   if (!g) return fail(SOCP_E_INVALID, "ingest is NULL");
   if (!g->shared) return fail(SOCP_E_INVALID, "the ingest was created without SOCP_F_SHARED_MATRICES");
   for (auto& sl : g->slot)
@@ -215,21 +259,37 @@ extern "C" int socp_ingest_set_matrices(socp_ingest* g, const double* A, const d
   if (!G || (d.m > 0 && !A)) return fail(SOCP_E_INVALID, "NULL data pointer");
   HIPCHK(hipSetDevice(g->ctx->device));
   const size_t bA = sizeof(double) * d.m * d.n, bG = sizeof(double) * d.k * d.n;
+  const size_t bP = sizeof(double) * d.n * d.n;
+  if (Pm && g->mat_P.ensure(bP)) return fail(SOCP_E_NOMEM, "device allocation failed");
   char* dm = (char*)g->mat.p;
   hipStream_t st = g->ctx->stream;
+  g->mat_qp = false;
+  if (Pm) HIPCHK(hipMemcpyAsync(g->mat_P.p, Pm, bP, hipMemcpyHostToDevice, st));
   if (bA) HIPCHK(hipMemcpyAsync(dm, A, bA, hipMemcpyHostToDevice, st));
   if (bG) HIPCHK(hipMemcpyAsync(dm + al_up(bA), G, bG, hipMemcpyHostToDevice, st));
   if (sing) HIPCHK(hipMemcpyAsync(dm + al_up(bA) + al_up(bG), sing, 1, hipMemcpyHostToDevice, st));
   HIPCHK(hipStreamSynchronize(st));
   g->mat_sing = sing != nullptr;
   g->have_mat = true;
+  g->mat_qp = Pm != nullptr;
   return 0;
+}
+
+extern "C" int socp_ingest_set_matrices(socp_ingest* g, const double* A, const double* G, const uint8_t* sing) {
+  return ingest_set_matrices_impl(g, nullptr, A, G, sing);
+}
+
+extern "C" int socp_ingest_set_matrices_qp(socp_ingest* g, const double* P, const double* A, const double* G,
+                                           const uint8_t* sing) {
+  return ingest_set_matrices_impl(g, P, A, G, sing);
 }
 
 // the part of submit shared by the dense and CSC forms: the slot's solve on the
 // context's stream after `ready`, and the result copies on the d2h stream
+// (P_dev: the QP solver kernels, socp_ingest_submit_qp)
 static int ingest_solve(socp_ingest* g, IngestSlot& sl, int64_t B, const uint8_t* sing_dev, bool have_sing,
-                        const socp_params* params, const double* A_dev, const double* G_dev) {
+                        const socp_params* params, const double* A_dev, const double* G_dev,
+                        const double* P_dev = nullptr) {
   socp_ctx* ctx = g->ctx;
   const socp_dims& d = g->dims;
   const InLayout Li = in_layout(d, d.batch, g->shared);
@@ -258,8 +318,11 @@ static int ingest_solve(socp_ingest* g, IngestSlot& sl, int64_t B, const uint8_t
   a.status = (int32_t*)(dout + Lo.st);
   a.res = (double*)(dout + Lo.res);
   a.counter = (int32_t*)g->counter.p;
+  const bool qp = P_dev != nullptr;
+  if (qp) small_set_qp(a, P_dev);
+  const SmallVariant* v = (qp && g->v && !g->v->qp_kernel) ? nullptr : g->v;  // (as batch_solve_impl)
   HIPCHK(hipStreamWaitEvent(ctx->stream, sl.ready, 0));
-  TRY(g->v ? launch_small(ctx, a, g->v) : launch_large(ctx, a));
+  TRY(v ? launch_small(ctx, a, v, qp) : launch_large(ctx, a, nullptr, qp));
   HIPCHK(hipEventRecord(sl.solved, ctx->stream));
   HIPCHK(hipStreamWaitEvent(g->d2h, sl.solved, 0));
   // one copy of the whole output block (x y z s iters status res err)
@@ -279,11 +342,29 @@ static int ingest_begin(socp_ingest* g, int64_t batch, IngestSlot** out) {
   return 0;
 }
 
-extern "C" int socp_ingest_submit(socp_ingest* g, int64_t batch, const double* c, const double* A, const double* b,
-                                  const double* G, const double* h, const uint8_t* sing, const socp_params* params,
-                                  int64_t* ticket) {
+// socp_ingest_submit, and socp_ingest_submit_qp (qp_entry): Pm the batch's matrices P on a
+// per-problem ingest (NULL: the linear solve); a shared ingest takes its P from
+// socp_ingest_set_matrices_qp
+static int ingest_submit_impl(socp_ingest* g, bool qp_entry, int64_t batch, const double* Pm, const double* c,
+                              const double* A, const double* b, const double* G, const double* h,
+                              const uint8_t* sing, const socp_params* params, int64_t* ticket) {
   if (params) TRY(check_detect_flags(params->flags));
   if (params) TRY(check_no_equilibrate(params->flags, "socp_ingest_submit"));
+  if (qp_entry && g && g->shared && Pm)
+    return fail(SOCP_E_INVALID, "shared ingest: P must be NULL (socp_ingest_set_matrices_qp gives it)");
+  if (qp_entry && g && g->shared && !g->mat_qp)
+    return fail(SOCP_E_INVALID, "shared ingest: socp_ingest_set_matrices_qp has not given a P");
+  const bool qp = qp_entry && g && (g->shared || Pm);
+  // the synchronous entry's refusals, before the slot is claimed
+  if (qp && params && (params->flags & SOCP_F_EXPLICIT_INVERSE))
+    return fail(SOCP_E_UNSUPPORTED,
+                "socp_ingest_submit_qp with SOCP_F_EXPLICIT_INVERSE: no QP kernel is compiled in the explicit-inverse "
+                "operation order");
+  if (qp && params && (params->flags & SOCP_F_DETECT_INFEASIBLE))
+    return fail(SOCP_E_UNSUPPORTED,
+                "socp_ingest_submit_qp with SOCP_F_DETECT_INFEASIBLE: the unboundedness rule would also need Px = 0, "
+                "which the detecting kernels do not test");
+  if (qp && !g->shared) TRY(ingest_ensure_P(g));
   IngestSlot* slp = nullptr;
   TRY(ingest_begin(g, batch, &slp));
   IngestSlot& sl = *slp;
@@ -311,21 +392,39 @@ extern "C" int socp_ingest_submit(socp_ingest* g, int64_t batch, const double* c
   // pinned -> device on the copy stream: one transfer per array
   for (int i = 0; i < 6; ++i)
     if (src[i] && nb[i]) HIPCHK(hipMemcpyAsync(din + off[i], pin + off[i], nb[i], hipMemcpyHostToDevice, g->h2d));
+  if (qp && !g->shared) {
+    const size_t bP = sizeof(double) * B * d.n * d.n;
+    par_copy(sl.pin_P, Pm, bP);
+    if (bP) HIPCHK(hipMemcpyAsync(sl.dev_P.p, sl.pin_P, bP, hipMemcpyHostToDevice, g->h2d));
+  }
   HIPCHK(hipEventRecord(sl.ready, g->h2d));
   if (B > 0 && g->shared) {
     const char* dm = (const char*)g->mat.p;
     const size_t oG = al_up(sizeof(double) * d.m * d.n), oS = oG + al_up(sizeof(double) * d.k * d.n);
     TRY(ingest_solve(g, sl, B, (const uint8_t*)(dm + oS), g->mat_sing, params, (const double*)dm,
-                     (const double*)(dm + oG)));
+                     (const double*)(dm + oG), qp ? (const double*)g->mat_P.p : nullptr));
   } else if (B > 0) {
     TRY(ingest_solve(g, sl, B, (const uint8_t*)(din + L.sing), sing != nullptr, params,
-                     (const double*)(din + L.A), (const double*)(din + L.G)));
+                     (const double*)(din + L.A), (const double*)(din + L.G),
+                     qp ? (const double*)sl.dev_P.p : nullptr));
   }
   sl.ticket = g->next++;
   sl.batch = B;
   sl.csc = false;
   *ticket = sl.ticket;
   return 0;
+}
+
+extern "C" int socp_ingest_submit(socp_ingest* g, int64_t batch, const double* c, const double* A, const double* b,
+                                  const double* G, const double* h, const uint8_t* sing, const socp_params* params,
+                                  int64_t* ticket) {
+  return ingest_submit_impl(g, false, batch, nullptr, c, A, b, G, h, sing, params, ticket);
+}
+
+extern "C" int socp_ingest_submit_qp(socp_ingest* g, int64_t batch, const double* P, const double* c,
+                                     const double* A, const double* b, const double* G, const double* h,
+                                     const uint8_t* sing, const socp_params* params, int64_t* ticket) {
+  return ingest_submit_impl(g, true, batch, P, c, A, b, G, h, sing, params, ticket);
 }
 
 // CSC form: A and G arrive as the SparseMatrixCSC arrays of socp_pack_csc;

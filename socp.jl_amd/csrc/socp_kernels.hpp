@@ -35,6 +35,9 @@ struct SmallVariant {
   // the pair's plain solver compiled for one exact launch geometry (KM = (pair << 4) | KM_EXACT,
   // socp_small.hpp ExactFit; gen_inst.py EXACT), else NULL: [SLOT_PAIR_* - 1]
   const void* exact_kernel[4];
+  // socp_batch_kkt_solve_qp / socp_dense_create_qp (KM 9): the plugin-entry kernel with P in H
+  const void* qp_kkt_kernel;
+  const char* qp_kkt_name;
 };
 
 // table of compiled register-resident variants, ordered by (NQ, NP, MQ)
@@ -127,7 +130,8 @@ struct LargeArgs {
 // gv: the problem's vectors in the HBM workspace instead of LDS (shapes whose
 // vectors exceed a CU's 160 KiB of LDS)
 // di: the solver with the infeasibility rule (SOCP_F_DETECT_INFEASIBLE; not with xi)
-// qp: the solver with the quadratic term P (socp_batch_solve_qp; with neither xi nor di)
+// qp: the kernels with the quadratic term P (socp_batch_solve_qp, and the QP plugin
+// entries in MODE_KKT / MODE_SETUP / MODE_SOLVEKKT; with neither xi nor di)
 const void* large_kernel_ptr(bool xi, bool gv, bool di = false, bool qp = false);
 const char* large_kernel_name(bool xi, bool gv, bool di = false, bool qp = false);
 

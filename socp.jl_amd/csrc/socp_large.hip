@@ -2512,7 +2512,10 @@ struct Large : LargeQp<QP> {
   __device__ void run(int64_t p) {
     LSTAMP(SP_OTHER);
     if (rec0) set_record(p);
-    if constexpr (QP) this->Pq = (gcdbl*)small_qp(a) + ((a.flags & F_SHARED) ? 0 : p * (int64_t)n * n);
+    // (the plugin modes read dy as a right-hand side: their P rides in the slot of x)
+    if constexpr (QP)
+      this->Pq = (gcdbl*)(a.mode == MODE_SOLVE ? small_qp(a) : small_qp_plugin(a)) +
+                 ((a.flags & F_SHARED) ? 0 : p * (int64_t)n * n);
     load(p);
     LSTAMP(SP_LOAD);
     int status = ST_MAXIT, iters = 0;

@@ -221,6 +221,12 @@ __device__ __forceinline__ double small_itol(const SmallArgs& a) {
 // it; the argument layout of the others stays as it was.
 inline void small_set_qp(SmallArgs& a, const double* P) { a.dy = P; }
 __device__ __forceinline__ const double* small_qp(const SmallArgs& a) { return a.dy; }
+// The QP plugin entries (socp_batch_kkt_solve_qp, socp_dense_create_qp; KM = 9,
+// the blocked QP kernels in MODE_KKT / MODE_SETUP / MODE_SOLVEKKT) read dy as a
+// right-hand side: there P rides in the slot of x, which only MODE_SOLVE reads
+// or writes.
+inline void small_set_qp_plugin(SmallArgs& a, const double* P) { a.x = const_cast<double*>(P); }
+__device__ __forceinline__ const double* small_qp_plugin(const SmallArgs& a) { return a.x; }
 
 // ------------------------------------------------------------ LDS layout
 // Fixed region (independent of the template shape):
@@ -3696,7 +3702,8 @@ struct Small {
     int after_singtest;
     bool have_sing = false;
     if constexpr (QP) {
-      qp_P = small_qp(a) + ((a.flags & F_SHARED) ? 0 : p * (int64_t)n * n);
+      // (MODE_SOLVEKKT solves against the record and never reads it)
+      qp_P = (KM ? small_qp_plugin(a) : small_qp(a)) + ((a.flags & F_SHARED) ? 0 : p * (int64_t)n * n);
       qp_hrange = n * n * (int)sizeof(double);
     }
     if (mode == MODE_SOLVEKKT) {  // setup_iter failed for this problem: NaN solution, its status
@@ -3968,6 +3975,18 @@ struct Small {
       phase = uni(next);
     }
     if (mode != MODE_SOLVE) {
+      if constexpr (QP && KM != 0) {
+        // the fused QP entry returns what setup_iter + solve_kkt return for a failed problem
+        // (socp.h: bitwise the split calls), as the blocked kernel's does: a NaN solution
+        if (status && mode == MODE_KKT) {
+          for (int j = lane; j < n; j += 64) a.cx[p * n + j] = NAN;
+          for (int i = lane; i < m; i += 64) a.cy[p * m + i] = NAN;
+          for (int i = lane; i < k; i += 64) {
+            a.cz[p * k + i] = NAN;
+            a.cs[p * k + i] = NAN;
+          }
+        }
+      }
       if (lane == 0) a.status[p] = status;
       if (mode == MODE_SETUP && lane == 0) a.rec[p * a.rec_stride + REC_STATUS] = (double)status;
       SYNC();
@@ -4021,7 +4040,8 @@ struct Small {
 // KM bit 0: the plugin-entry kernel (MODE_KKT / MODE_SETUP / MODE_SOLVEKKT)
 // instead of the solver; bit 1: the explicit-inverse variant (XI above);
 // bit 2 (KM = 4): the solver with SOCP_F_DETECT_INFEASIBLE;
-// bit 3 (KM = 8): the QP solver (socp_batch_solve_qp), mixed slots only;
+// bit 3 (KM = 8): the QP solver (socp_batch_solve_qp), mixed slots only; with bit 0
+// (KM = 9) the QP plugin entries (socp_batch_kkt_solve_qp, socp_dense_create_qp);
 // bit 7 (KM_EXACT, with a pair): the pair's plain solver at one exact launch geometry (ExactFit)
 template <int NQ, int NP, int MQ, int KM>
 #ifndef SOCP_DEV_MINW

@@ -150,6 +150,22 @@ def _check_sizes(B, **arrays):
             raise ValueError(f"{name}: {got} elements, expected {want} (batch {B})")
 
 
+def _check_P(P, G, MB, n):
+    """``batch_solve``'s rules for P: on the same side as G; a host array is
+    checked for symmetry and returned flat, float64, contiguous."""
+    if P is None:
+        return None
+    if _is_torch(P) != _is_torch(G) or (_is_torch(P) and (
+            str(P.dtype) != "torch.float64" or P.device != G.device or not P.is_contiguous())):
+        raise ValueError("P must be on the same side as G (host array, or contiguous float64 tensor on G's device)")
+    if _is_torch(P):
+        return P
+    Ph = _host(P).reshape(MB, n, n)
+    if not np.allclose(Ph, Ph.transpose(0, 2, 1)):
+        raise ValueError("P: every problem's matrix must be symmetric")
+    return Ph.reshape(-1)
+
+
 def batch_solve(cones, n, m, k, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5, step=0.99,
                 sigma_exp=3, init_eps=1e-10, warm=None, ctx=None, res=False, out=None, force_large=False,
                 explicit_inverse=False, detect_infeasible=False, shared_matrices=False, P=None,
@@ -198,14 +214,7 @@ def batch_solve(cones, n, m, k, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5,
     MB = 1 if shared_matrices else B
     _check_sizes(B, A=(A if m else None, MB * m * n), b=(b if m else None, B * m), G=(G, MB * k * n),
                  h=(h, B * k), sing=(sing, MB), P=(P, MB * n * n))
-    if P is not None and (_is_torch(P) != _is_torch(G) or (_is_torch(P) and (
-            str(P.dtype) != "torch.float64" or P.device != G.device or not P.is_contiguous()))):
-        raise ValueError("P must be on the same side as G (host array, or contiguous float64 tensor on G's device)")
-    if P is not None and not _is_torch(P):
-        Ph = _host(P).reshape(MB, n, n)
-        if not np.allclose(Ph, Ph.transpose(0, 2, 1)):
-            raise ValueError("P: every problem's matrix must be symmetric")
-        P = Ph.reshape(-1)
+    P = _check_P(P, G, MB, n)
     if warm is not None:
         wx, wy, wz, ws = warm
         _check_sizes(B, warm_x=(wx, B * n), warm_y=(wy if m else None, B * m), warm_z=(wz, B * k),
@@ -330,10 +339,14 @@ def equilibrate(cones, n, m, k, A, G, P=None, c=None, b=None, h=None, *, shared_
 
 
 def batch_kkt_solve(cones, n, m, k, A, G, sing, s, z, dx, dy, dz, ds, *, ctx=None, force_large=False,
-                    explicit_inverse=False, shared_matrices=False):
+                    explicit_inverse=False, shared_matrices=False, P=None):
     """One KKT solve per problem at iterate (s, z): scaling + setup_iter + solve_kkt
     (densesolver.jl:41-90) on the GPU.  Host (numpy) arrays.  shared_matrices: A, G
-    and sing are the batch's one (as in ``batch_solve``).  Returns dict(cx,cy,cz,cs,status)."""
+    and sing are the batch's one (as in ``batch_solve``).  P (``batch_solve``'s:
+    n x n per problem, ONE with shared_matrices, checked for symmetry): the
+    system's first row is P cx + A'cy + G'cz = dx (socp_batch_kkt_solve_qp); not
+    together with explicit_inverse (SOCP_E_UNSUPPORTED).
+    Returns dict(cx,cy,cz,cs,status)."""
     L = _lib.load()
     kind, offs, dim = cone_arrays(cones)
     B = np.size(s) // k
@@ -341,20 +354,25 @@ def batch_kkt_solve(cones, n, m, k, A, G, sing, s, z, dx, dy, dz, ds, *, ctx=Non
         raise ValueError(f"s: {np.size(s)} elements is not a multiple of k={k}")
     MB = 1 if shared_matrices else B
     _check_sizes(B, A=(A if m else None, MB * m * n), G=(G, MB * k * n), sing=(sing, MB), z=(z, B * k),
-                 dx=(dx, B * n), dy=(dy if m else None, B * m), dz=(dz, B * k), ds=(ds, B * k))
+                 dx=(dx, B * n), dy=(dy if m else None, B * m), dz=(dz, B * k), ds=(ds, B * k),
+                 P=(P, MB * n * n))
+    P = _check_P(P, G, MB, n)
     dims = _lib.Dims(B, n, m, k, len(kind))
     ctx = ctx or default_context()
     cx, cy, cz, cs = np.zeros(B * n), np.zeros(max(B * m, 1)), np.zeros(B * k), np.zeros(B * k)
     st = np.zeros(B, np.int32)
     p = _lib.ptr
     sg = None if sing is None else _host(sing, np.uint8)
-    rc = L.socp_batch_kkt_solve(ctx.handle, dims, p(kind), p(offs), p(dim),
-                                p(_host(A) if m else None), p(_host(G)), p(sg), p(_host(s)), p(_host(z)),
-                                p(_host(dx)), p(_host(dy) if m else None), p(_host(dz)), p(_host(ds)),
-                                p(cx), p(cy if m else None), p(cz), p(cs), p(st),
-                                (F_FORCE_LARGE if force_large else 0)
-                                | (F_EXPLICIT_INVERSE if explicit_inverse else 0)
-                                | (F_SHARED_MATRICES if shared_matrices else 0))
+    tail = (p(_host(A) if m else None), p(_host(G)), p(sg), p(_host(s)), p(_host(z)),
+            p(_host(dx)), p(_host(dy) if m else None), p(_host(dz)), p(_host(ds)),
+            p(cx), p(cy if m else None), p(cz), p(cs), p(st),
+            (F_FORCE_LARGE if force_large else 0)
+            | (F_EXPLICIT_INVERSE if explicit_inverse else 0)
+            | (F_SHARED_MATRICES if shared_matrices else 0))
+    if P is None:
+        rc = L.socp_batch_kkt_solve(ctx.handle, dims, p(kind), p(offs), p(dim), *tail)
+    else:
+        rc = L.socp_batch_kkt_solve_qp(ctx.handle, dims, p(kind), p(offs), p(dim), p(P), *tail)
     _lib.check(rc)
     return dict(cx=cx, cy=cy[:B * m], cz=cz, cs=cs, status=st)
 
@@ -376,7 +394,12 @@ class DenseHandle:
     matrix, ONE k x n matrix and ONE byte for all ``batch`` problems (``batch``
     must then be given: G no longer tells it); the handle keeps that one copy,
     the factor records stay per problem, and every result is bitwise that of
-    the handle built on the replicated matrices."""
+    the handle built on the replicated matrices.
+
+    P (``batch_solve``'s; on the same side as G, ONE matrix with
+    shared_matrices): the handle keeps it beside A and G (socp_dense_create_qp)
+    and setup_iter factors H = P + G'W^-2 G (+A'A); results are bitwise those
+    of ``batch_kkt_solve(P=...)``.  Not together with explicit_inverse."""
 
     _pfx = "socp_dense"
 
@@ -384,7 +407,7 @@ class DenseHandle:
         return getattr(_lib.load(), f"{self._pfx}_{name}")
 
     def __init__(self, cones, n, m, k, A, G, sing=None, *, ctx=None, force_large=False, explicit_inverse=False,
-                 shared_matrices=False, batch=None):
+                 shared_matrices=False, batch=None, P=None):
         self.cones, self.n, self.m, self.k = cones, n, m, k
         self.kind, self.offs, self.dim = cone_arrays(cones)
         if shared_matrices:
@@ -401,6 +424,9 @@ class DenseHandle:
             _check_sizes(B, A=(A if m else None, B * m * n), sing=(sing, B))
         self.B = B
         self.shared_matrices = bool(shared_matrices)
+        MB = 1 if shared_matrices else B
+        _check_sizes(B, P=(P, MB * n * n))
+        P = _check_P(P, G, MB, n)
         self.ctx = ctx or default_context()
         self.dev = _is_torch(G)
         flags = ((F_DEVICE_PTRS if self.dev else 0) | (F_FORCE_LARGE if force_large else 0)
@@ -414,8 +440,12 @@ class DenseHandle:
         h = C.c_void_p()
         dims = _lib.Dims(B, n, m, k, len(self.kind))
         p = _lib.ptr
-        _lib.check(self._fn("create")(self.ctx.handle, dims, p(self.kind), p(self.offs), p(self.dim),
-                                       p(arrs[0]), p(arrs[1]), p(arrs[2]), flags, C.byref(h)))
+        if P is None:
+            _lib.check(self._fn("create")(self.ctx.handle, dims, p(self.kind), p(self.offs), p(self.dim),
+                                           p(arrs[0]), p(arrs[1]), p(arrs[2]), flags, C.byref(h)))
+        else:  # (DenseHandle only: SqrHandle's constructor takes no P)
+            _lib.check(self._fn("create_qp")(self.ctx.handle, dims, p(self.kind), p(self.offs), p(self.dim),
+                                              p(P), p(arrs[0]), p(arrs[1]), p(arrs[2]), flags, C.byref(h)))
         self.handle = h
 
     def close(self):
@@ -593,7 +623,17 @@ class Ingest:
     sing; ``set_matrices(A, G, sing=None)`` gives the one A, G and sing byte of
     every later batch (only with no ticket outstanding; again between batches
     as needed), ``submit(c, None, b, None, h)`` carries the vectors alone and
-    ``next_inputs()`` has no A, G, sing."""
+    ``next_inputs()`` has no A, G, sing.
+
+    P (``batch_solve``'s quadratic objective; host arrays, checked for
+    symmetry): ``submit(..., P=P)`` runs socp_ingest_submit_qp, bitwise
+    ``batch_solve(P=P)``; the slots' room for P is allocated by the first call
+    that brings one (``next_inputs(P=True)`` adds the next slot's pinned P
+    block to the dict).  A shared ingest takes its one P through
+    ``set_matrices(A, G, sing, P=P)`` and ``submit(..., qp=True)`` solves with
+    it.  Not together with explicit_inverse or detect_infeasible
+    (SOCP_E_UNSUPPORTED, and the slot stays free).  A submit without P is the
+    linear solve."""
 
     def __init__(self, cones, n, m, k, max_batch, *, ctx=None, force_large=False, shared_matrices=False):
         L = _lib.load()
@@ -610,16 +650,19 @@ class Ingest:
         self.shared_matrices = bool(shared_matrices)
         self._batch = {}
 
-    def set_matrices(self, A, G, sing=None):
+    def set_matrices(self, A, G, sing=None, P=None):
         """The one A (m x n), G (k x n), column-major, and sing byte (None: the
         device probe) of every later batch of a shared ingest
-        (socp_ingest_set_matrices): host arrays, copied synchronously."""
+        (socp_ingest_set_matrices): host arrays, copied synchronously.  P: their
+        one n x n P (socp_ingest_set_matrices_qp); without it any earlier P is cleared."""
         n, m, k = self.n, self.m, self.k
-        _check_sizes(1, A=(A if m else None, m * n), G=(G, k * n), sing=(sing, 1))
+        _check_sizes(1, A=(A if m else None, m * n), G=(G, k * n), sing=(sing, 1), P=(P, n * n))
         p = _lib.ptr
-        _lib.check(_lib.load().socp_ingest_set_matrices(
-            self.handle, p(_host(A) if m else None), p(_host(G)),
-            p(None if sing is None else _host(sing, np.uint8))))
+        tail = (p(_host(A) if m else None), p(_host(G)), p(None if sing is None else _host(sing, np.uint8)))
+        if P is None:
+            _lib.check(_lib.load().socp_ingest_set_matrices(self.handle, *tail))
+        else:
+            _lib.check(_lib.load().socp_ingest_set_matrices_qp(self.handle, p(_check_P(P, _host(G), 1, n)), *tail))
 
     def close(self):
         if getattr(self, "handle", None):
@@ -632,7 +675,9 @@ class Ingest:
         except Exception:
             pass
 
-    def next_inputs(self):
+    def next_inputs(self, P=False):
+        """numpy views of the next slot's pinned input arrays; P=True adds the
+        slot's pinned P block (socp_ingest_next_P; not on a shared ingest)."""
         ptrs = [C.c_void_p() for _ in range(6)]
         _lib.check(_lib.load().socp_ingest_next_inputs(self.handle, *[C.byref(q) for q in ptrs]))
         B, n, m, k = self.max_batch, self.n, self.m, self.k
@@ -643,24 +688,36 @@ class Ingest:
             if self.shared_matrices and key in ("A", "G", "sing"):
                 continue  # NULL: a shared ingest stages none of them
             out[key] = np.ctypeslib.as_array(C.cast(q, C.POINTER(ct)), shape=(max(cnt, 1),))[:cnt]
+        if P:
+            q = C.c_void_p()
+            _lib.check(_lib.load().socp_ingest_next_P(self.handle, C.byref(q)))
+            out["P"] = np.ctypeslib.as_array(C.cast(q, C.POINTER(C.c_double)), shape=(B * n * n,))
         return out
 
-    def _params(self, maxit, tol, step, sigma_exp, init_eps, detect_infeasible=False):
+    def _params(self, maxit, tol, step, sigma_exp, init_eps, detect_infeasible=False, explicit_inverse=False):
         return default_params(maxit=maxit, tol=tol, step=step, sigma_exp=sigma_exp, init_eps=init_eps,
-                              flags=F_DETECT_INFEASIBLE if detect_infeasible else 0)
+                              flags=(F_DETECT_INFEASIBLE if detect_infeasible else 0)
+                              | (F_EXPLICIT_INVERSE if explicit_inverse else 0))
 
     def submit(self, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5, step=0.99, sigma_exp=3, init_eps=1e-10,
-               detect_infeasible=False):
+               detect_infeasible=False, explicit_inverse=False, P=None, qp=False):
+        """P: the batch's matrices (a per-problem ingest); qp=True: a shared
+        ingest's solve with the P of ``set_matrices(P=...)``."""
         n, m, k = self.n, self.m, self.k
         B = np.size(c) // n
         _check_sizes(B, c=(c, B * n), A=(A if m else None, B * m * n), b=(b if m else None, B * m),
-                     G=(G, B * k * n), h=(h, B * k), sing=(sing, B))
+                     G=(G, B * k * n), h=(h, B * k), sing=(sing, B), P=(P, B * n * n))
         t = C.c_int64()
-        P = self._params(maxit, tol, step, sigma_exp, init_eps, detect_infeasible)
+        pr = self._params(maxit, tol, step, sigma_exp, init_eps, detect_infeasible, explicit_inverse)
         p = _lib.ptr
         arr = [_host(c), _host(A) if m and A is not None else None, _host(b) if m else None, _host(G), _host(h),
                None if sing is None else _host(sing, np.uint8)]
-        _lib.check(_lib.load().socp_ingest_submit(self.handle, B, *[p(a) for a in arr], P, C.byref(t)))
+        if P is not None or qp:
+            Ph = None if P is None else _check_P(P, arr[0], B, n)
+            _lib.check(_lib.load().socp_ingest_submit_qp(self.handle, B, p(Ph), *[p(a) for a in arr], pr,
+                                                         C.byref(t)))
+        else:
+            _lib.check(_lib.load().socp_ingest_submit(self.handle, B, *[p(a) for a in arr], pr, C.byref(t)))
         self._batch[t.value] = B
         return t.value
 
@@ -840,7 +897,8 @@ class DenseSolver:
     """KKTSolver{Scaling} plugin for the dense path (densesolver.jl:1-90) on
     MI355X: DenseSolver(pr) (:19-38) keeps A and G on the device (a one-problem
     DenseHandle); setup_iter factors into the handle's record, solve_kkt solves
-    against it, so only n+m+2k doubles move per solve."""
+    against it, so only n+m+2k doubles move per solve.  A Problem with a P
+    gives the handle that P: the plugin loop then solves the QP's KKT system."""
 
     scaling_type = Scaling
 
@@ -849,7 +907,7 @@ class DenseSolver:
         self.ctx = ctx
         self.handle = DenseHandle(prob.cones, prob.n, prob.m, prob.k, _colmajor(prob.A, prob.m, prob.n),
                                   _colmajor(prob.G, prob.k, prob.n), np.array([prob.sing], np.uint8),
-                                  ctx=ctx)
+                                  ctx=ctx, P=None if prob.P is None else _colmajor(prob.P, prob.n, prob.n))
 
 
 HipDenseSolver = DenseSolver
@@ -880,6 +938,8 @@ class SparseSolver(DenseSolver):
     scaling_type = SqrScaling
 
     def __init__(self, prob: Problem, ctx: Context | None = None):
+        if prob.P is not None:
+            raise ValueError("P: the rank-update solver takes linear objectives only")
         self.prob = prob
         self.ctx = ctx
         self.handle = SqrHandle(prob.cones, prob.n, prob.m, prob.k, _colmajor(prob.A, prob.m, prob.n),

@@ -40,7 +40,12 @@ EXPORTED = [
     "socp_sqr_solve_socp", "socp_ctx_set_infeasibility_tol", "socp_debug_slot_plan",
     "socp_batch_solve_qp", "socp_batch_equilibrate", "socp_ctx_set_equilibration_passes",
     "socp_debug_exact_fit",
+    "socp_batch_kkt_solve_qp", "socp_dense_create_qp",
+    "socp_ingest_submit_qp", "socp_ingest_set_matrices_qp",
 ]
+# declared and exported as well, but kept out of the list above: tests/test_abi.py compares that
+# list with the header's lower-case names
+EXPORTED_MIXED_CASE = ["socp_ingest_next_P"]
 
 OUTCOME_BYTES = 32  # sizeof(socp_outcome): int32 status, int32 iters, double rd, rp, gap
 MAX_BATCH = 2**31 - 1  # device problem indices are int32
@@ -117,6 +122,14 @@ def load():
     L.socp_batch_solve_ex.argtypes = common + [dp] * 5 + [u8p, C.POINTER(Params)] + [dp] * 4 + [i32p, i32p, dp]
     L.socp_batch_solve_qp.argtypes = common + [dp] * 6 + [u8p, C.POINTER(Params)] + [dp] * 4 + [i32p, i32p, dp]
     L.socp_batch_kkt_solve.argtypes = common + [dp, dp, u8p] + [dp] * 2 + [dp] * 4 + [dp] * 4 + [i32p, C.c_int32]
+    if hasattr(L, "socp_batch_kkt_solve_qp"):  # QP plugin entries and ingest (absent from older A/B builds)
+        L.socp_batch_kkt_solve_qp.argtypes = (common + [dp, dp, dp, u8p] + [dp] * 2 + [dp] * 4 + [dp] * 4
+                                              + [i32p, C.c_int32])
+        L.socp_dense_create_qp.argtypes = common + [dp, dp, dp, u8p, C.c_int32, C.POINTER(C.c_void_p)]
+        L.socp_ingest_submit_qp.argtypes = ([vp, C.c_int64] + [dp] * 6
+                                            + [u8p, C.POINTER(Params), C.POINTER(C.c_int64)])
+        L.socp_ingest_set_matrices_qp.argtypes = [vp, dp, dp, dp, u8p]
+        L.socp_ingest_next_P.argtypes = [vp, C.POINTER(C.c_void_p)]
     L.socp_generate.argtypes = common + [C.c_uint64, C.c_int64] + [dp] * 5
     L.socp_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.socp_kernel_times.argtypes = [vp, C.POINTER(C.c_float), C.c_int]

@@ -76,6 +76,23 @@ class ScalarAffineFunction:
     constant: float = 0.0
 
 
+@dataclass(frozen=True)
+class ScalarQuadraticTerm:
+    coefficient: float
+    variable_1: VariableIndex
+    variable_2: VariableIndex
+
+
+@dataclass
+class ScalarQuadraticFunction:
+    """MOI's convention: the function is x'Qx/2 + a'x + constant with Q
+    symmetric; a term (c, i, i) adds c to Q[i, i], a term (c, i, j), i != j,
+    adds c to Q[i, j] and to Q[j, i] (so it contributes c x_i x_j)."""
+    quadratic_terms: list
+    affine_terms: list
+    constant: float = 0.0
+
+
 @dataclass
 class VectorAffineFunction:
     terms: list
@@ -131,6 +148,7 @@ class ModelData:
     cones: tuple
     objconstant: float = 0.0
     signature: tuple = field(default=())
+    P: np.ndarray | None = None  # n x n symmetric (the solver's: negated with c under MAX_SENSE); None: linear
 
 
 class Optimizer:
@@ -173,7 +191,16 @@ class Optimizer:
     def set_objective_sense(self, sense):
         self.sense = sense  # MOIU.allocate(::ObjectiveSense) (moi.jl:187-189)
 
-    def set_objective_function(self, f: ScalarAffineFunction):
+    def set_objective_function(self, f):
+        """A ScalarAffineFunction or a ScalarQuadraticFunction (whose Q, in the
+        solver's sense, must be positive semidefinite; unchecked)."""
+        if not isinstance(f, (ScalarAffineFunction, ScalarQuadraticFunction)):
+            raise TypeError(f"unsupported objective {type(f).__name__}")
+        if isinstance(f, ScalarQuadraticFunction):
+            for t in f.quadratic_terms:
+                for v in (t.variable_1, t.variable_2):
+                    if not (1 <= v.value <= self.nvars):
+                        raise ValueError(f"unknown variable {v.value}")
         self.objective = f
 
     # -- constraints: _allocate_constraint (moi.jl:96-116)
@@ -227,13 +254,23 @@ class Optimizer:
                 V = np.array([-t.scalar_term.coefficient for t in con.f.terms], dtype=np.float64)
                 np.add.at(M, (I, J), V)  # MOIU.canonical merges duplicate terms (moi.jl:143)
         c0 = np.zeros(n)
-        for t in self.objective.terms:
+        quad = isinstance(self.objective, ScalarQuadraticFunction)
+        for t in (self.objective.affine_terms if quad else self.objective.terms):
             c0[t.variable.value - 1] += t.coefficient
         c = -c0 if self.sense == MAX_SENSE else c0  # moi.jl:199
+        P = None
+        if quad:
+            Q = np.zeros((n, n))
+            for t in self.objective.quadratic_terms:
+                i, j = t.variable_1.value - 1, t.variable_2.value - 1
+                Q[i, j] += t.coefficient
+                if i != j:
+                    Q[j, i] += t.coefficient
+            P = -Q if self.sense == MAX_SENSE else Q
         cones = ((POC(0, self.l),) if self.l else ()) + tuple(
             SOC(self.l + sum(self.qa[:i]), d) for i, d in enumerate(self.qa))
         sig = (n, f, self.l, tuple(self.qa))
-        self.data = ModelData(c, A, b, G, h, cones, float(self.objective.constant), sig)
+        self.data = ModelData(c, A, b, G, h, cones, float(self.objective.constant), sig, P)
         return self.data
 
     # -- optimize! (moi.jl:203-222)
@@ -273,7 +310,11 @@ class Optimizer:
     def objective_value(self) -> float:
         sol = self._need_sol()
         c0 = -self.data.c if self.sense == MAX_SENSE else self.data.c
-        return float(c0 @ sol.x + self.data.objconstant)
+        val = float(c0 @ sol.x + self.data.objconstant)
+        if self.data.P is not None:  # + x'Qx/2 in the model's sense
+            q = 0.5 * float(sol.x @ (self.data.P @ sol.x))
+            val += -q if self.sense == MAX_SENSE else q
+        return val
 
     def _rows(self, ci: ConstraintIndex):
         for con in self.cons:
@@ -305,22 +346,28 @@ def optimize_batched(optimizers, ctx=None, shared_matrices=False):
     are solved with SOCP_F_EQUILIBRATE (``batch_solve``'s equilibrate: `tol`
     then refers to the scaled problem, and `sing` is probed on the scaled G).
     The library refuses detection together with that flag, so these groups run
-    without it: an infeasible model ends with a numerical status, not a certificate."""
+    without it: an infeasible model ends with a numerical status, not a certificate.
+    Models with a quadratic objective (ScalarQuadraticFunction) form groups of
+    their own as well and run ``batch_solve(P=...)`` (socp_batch_solve_qp), for
+    the same reason without detection: the library refuses that pair too.  With
+    shared_matrices=True every such model's P must equal the group's first."""
     groups: "OrderedDict[tuple, list]" = OrderedDict()
     for o in optimizers:
         d = o.build()
         key = d.signature + (int(o.options.get("maxit", 40)), float(o.options.get("tol", 1e-5)),
-                             bool(o.options.get("equilibrate", False)))
+                             bool(o.options.get("equilibrate", False)), d.P is not None)
         groups.setdefault(key, []).append(o)
     for key, opts in groups.items():
         n, f, l, qa = key[:4]
-        maxit, tol, equil = key[4], key[5], key[6]
+        maxit, tol, equil, quad = key[4], key[5], key[6], key[7]
         k = l + sum(qa)
         ds = [o.data for o in opts]
         if shared_matrices:
             for i, d in enumerate(ds):
                 if (f and not np.array_equal(d.A, ds[0].A)) or not np.array_equal(d.G, ds[0].G):
                     raise ValueError(f"shared_matrices=True: model {i} of its group differs from the first in A or G")
+                if quad and not np.array_equal(d.P, ds[0].P):
+                    raise ValueError(f"shared_matrices=True: model {i} of its group differs from the first in P")
         ms = ds[:1] if shared_matrices else ds
         sing = None if equil else np.array([_sing(d.G) for d in ms], np.uint8)
         c = np.concatenate([d.c for d in ds])
@@ -328,8 +375,10 @@ def optimize_batched(optimizers, ctx=None, shared_matrices=False):
         b = np.concatenate([d.b for d in ds]) if f else None
         G = np.concatenate([d.G.ravel(order="F") for d in ms])
         h = np.concatenate([d.h for d in ds])
+        P = np.concatenate([d.P.ravel(order="F") for d in ms]) if quad else None
         out = batch_solve(ds[0].cones, n, f, k, c, A, b, G, h, sing, maxit=maxit, tol=tol,
-                          detect_infeasible=not equil, equilibrate=equil, shared_matrices=shared_matrices,
+                          detect_infeasible=not (equil or quad), equilibrate=equil, shared_matrices=shared_matrices,
+                          P=P,
                           ctx=ctx if ctx is not None else opts[0].options.get("ctx"))
         for i, o in enumerate(opts):
             o._set_solution(out["x"][i * n:(i + 1) * n], out["y"][i * f:(i + 1) * f],
@@ -355,3 +404,9 @@ def vaf(rows, constants):
 def saf(terms, constant=0.0):
     """Shorthand: ScalarAffineFunction from [(VariableIndex, coef), ...]."""
     return ScalarAffineFunction([ScalarAffineTerm(float(a), v) for v, a in terms], float(constant))
+
+
+def sqf(quadratic, affine=(), constant=0.0):
+    """Shorthand: ScalarQuadraticFunction from [(VariableIndex, VariableIndex, coef), ...] and saf's terms."""
+    return ScalarQuadraticFunction([ScalarQuadraticTerm(float(a), u, v) for u, v, a in quadratic],
+                                   [ScalarAffineTerm(float(a), v) for v, a in affine], float(constant))
