@@ -117,6 +117,17 @@ int host::check_no_equilibrate(int32_t flags, const char* who) {
   return 0;
 }
 
+// the flags no QP kernel is compiled for, refused by the QP entry `who` (include/socp.h)
+int host::check_qp_flags(int32_t flags, const char* who) {
+  if (flags & SOCP_F_EXPLICIT_INVERSE)
+    return fail(SOCP_E_UNSUPPORTED, std::string(who) + " with SOCP_F_EXPLICIT_INVERSE: no QP kernel is compiled in the "
+                                                       "explicit-inverse operation order");
+  if (flags & SOCP_F_DETECT_INFEASIBLE)
+    return fail(SOCP_E_UNSUPPORTED, std::string(who) + " with SOCP_F_DETECT_INFEASIBLE: the unboundedness rule would "
+                                                       "also need Px = 0, which the detecting kernels do not test");
+  return 0;
+}
+
 // SOCP_F_DETECT_INFEASIBLE with SOCP_F_EXPLICIT_INVERSE: refused (include/socp.h)
 int host::check_detect_flags(int32_t flags) {
   if ((flags & SOCP_F_DETECT_INFEASIBLE) && (flags & SOCP_F_EXPLICIT_INVERSE))
@@ -224,7 +235,7 @@ int host::check_problem(const socp_dims* d, const int32_t* kind, const int32_t* 
   return 0;
 }
 
-const SmallVariant* host::pick_variant(int n, int m, int k) {
+static const SmallVariant* pick_variant(int n, int m, int k) {
   int cnt = 0;
   const SmallVariant* v = small_variants(&cnt);
   const SmallVariant* best = nullptr;
@@ -244,7 +255,7 @@ const SmallVariant* host::pick_variant(int n, int m, int k) {
 // The blocked kernel (socp_large.hip): n, m <= 2048.  The problem's vectors live in the 160 KiB LDS of a CU when
 // they fit; otherwise (e.g. k = 1000 at n = 512) in the workgroup's slot of the
 // HBM workspace (*gv: the GV kernels), with only the problem index in LDS.
-bool host::large_fits(int n, int m, int k, int nc, size_t* lds_bytes, bool* gv) {
+static bool large_fits(int n, int m, int k, int nc, size_t* lds_bytes, bool* gv = nullptr) {
   // Every LDS / vector offset of the kernel (LargeLayout::o_*, total, LV(int))
   // is a 32-bit int and X = W^-1 G (KP x NPAD) is addressed from int row
   // offsets: bound k before the layout is computed in int, so that neither
@@ -269,15 +280,26 @@ bool host::large_fits(int n, int m, int k, int nc, size_t* lds_bytes, bool* gv) 
   return true;
 }
 
-extern "C" int socp_supported(const socp_dims* d) {
-  if (!d) return 0;
-  if (pick_variant(d->n, d->m, d->k) != nullptr && d->ncones <= NCS) return 1;
-  return large_fits(d->n, d->m, d->k, d->ncones, nullptr) ? 1 : 0;
-}
-
 const char* const host::kUnsupported =
     "dims outside both kernels (register-resident: n, m <= 64, k <= 128, <= 8 cones; "
     "blocked: n, m <= 2048, <= 64 cones, k <= 2^21)";
+
+// Which engine runs a call of these dims that wants kernel `kind`: the register kernel's cheapest variant
+// that holds them (*v), or the blocked kernel (*v = NULL) -- with SOCP_F_FORCE_LARGE, with more than NCS
+// cones, and where the variant has no kernel of the kind.  false: the dims fit neither (no error text is set).
+static bool engine_fits(const socp_dims& d, int32_t flags, SmallKind kind, const SmallVariant** v) {
+  *v = ((flags & SOCP_F_FORCE_LARGE) || d.ncones > NCS) ? nullptr : pick_variant(d.n, d.m, d.k);
+  if (*v && !(*v)->k[kind].fn) *v = nullptr;
+  return *v || large_fits(d.n, d.m, d.k, d.ncones, nullptr);
+}
+int host::choose_engine(const socp_dims& d, int32_t flags, SmallKind kind, const SmallVariant** v) {
+  return engine_fits(d, flags, kind, v) ? 0 : fail(SOCP_E_UNSUPPORTED, kUnsupported);
+}
+
+extern "C" int socp_supported(const socp_dims* d) {
+  const SmallVariant* v = nullptr;
+  return d && engine_fits(*d, 0, KIND_SOLVE, &v) ? 1 : 0;
+}
 
 // ---------------------------------------------------------------- launch
 static unsigned long long* g_stamps = nullptr;  // per-phase cycle table (SOCP_DIAG builds)
@@ -301,7 +323,7 @@ static int cone_rows_uniform(const ConeTable& t, int nc) {
 // SOCP_INIT_OVERLAP: the initial point's G'G is formed by form_H's row loop on every kernel,
 // not under G's load in load_problem
 // SOCP_EXACT_FIT: a launch that fills its variant exactly runs the pair's generic pure-slot
-// kernel, not the one compiled for its geometry (small_exact_pair)
+// kernel, not the one compiled for its geometry (small_select)
 static bool env_enabled(const char* name) {
   const char* e = getenv(name);
   return !(e && e[0] == '0' && e[1] == '\0');
@@ -312,10 +334,7 @@ extern "C" int socp_debug_slot_plan(const socp_dims* d, const int32_t* kind, con
   ConeTable tab;
   int deg = 0;
   if (!rot || !kind0 || !kind1) return fail(SOCP_E_INVALID, "output pointers are NULL");
-  {
-    const int rc = check_problem(d, kind, offs, dim, &tab, &deg);
-    if (rc) return rc;
-  }  // the tables a solve takes, no others
+  TRY(check_problem(d, kind, offs, dim, &tab, &deg));  // the tables a solve takes, no others
   int32_t r = 0, kk = 0;
   small_slot_plan(tab, tab.nc, d->k, cone_rows_uniform(tab, tab.nc), env_enabled("SOCP_SLOT_SPECIALISE"), r, kk);
   *rot = r;
@@ -324,8 +343,10 @@ extern "C" int socp_debug_slot_plan(const socp_dims* d, const int32_t* kind, con
   return 0;
 }
 
-// al_rows and fuse_u of a launch of variant v (args.cones, args.nc set)
-static void small_cone_geometry(SmallArgs& args, const SmallVariant* v) {
+// Which kernel of variant v a launch runs (*out), and what the choice sets in its arguments:
+// al_rows, fuse_u, slot_rot, slot_kinds and init_overlap.  args: mode, flags, dims and cone
+// table set; qp: the call carries a P.  Host logic only.
+int host::small_select(const SmallVariant* v, SmallArgs& args, bool qp, SmallKernel* out) {
   args.al_rows = cone_rows_uniform(args.cones, args.nc);
   // (cones of 32 or 64 rows on a variant of whole 8-row-step chunks: a G x chunk lies in one cone)
   args.fuse_u = 0;
@@ -334,99 +355,90 @@ static void small_cone_geometry(SmallArgs& args, const SmallVariant* v) {
     for (int c = 0; c < args.nc && c < NCS; ++c)
       if (args.cones.kind[c] == SOC_K) args.fuse_u |= 1 << c;
   }
-}
-
-// The pure-slot pair (SLOT_PAIR_*) whose exact-fit kernel this plain solve takes, or
-// SLOT_PAIR_NONE: the slot plan chose a pair, variant v has that pair's exact-fit kernel, and
-// dims, cone table, al_rows, slot_rot and fuse_u are the ones it was compiled for
-// (small_exact_fit: SOCP_FUSE_U=0 or SOCP_SLOT_SPECIALISE=0 so leave none).
-// args: cones, nc, n, m, k, al_rows, fuse_u, slot_rot, slot_kinds set.
-static int small_exact_pair(const SmallArgs& args, const SmallVariant* v) {
-  const int pair = slot_pair_of(args.slot_kinds & 15, args.slot_kinds >> 4);
-  if (pair == SLOT_PAIR_NONE || !v->exact_kernel[pair - 1] || !env_enabled("SOCP_EXACT_FIT")) return SLOT_PAIR_NONE;
-  return small_exact_fit(args, v->NQ, v->NP, v->MQ, pair) ? pair : SLOT_PAIR_NONE;
+  const bool solver = args.mode == MODE_SOLVE;
+  // SOCP_F_EXPLICIT_INVERSE: the explicit-inverse variants (m <= 16 shapes; larger m form Li anyway)
+  const bool xi = (args.flags & SOCP_F_EXPLICIT_INVERSE) != 0 && v->k[KIND_XI].fn;
+  // SOCP_F_DETECT_INFEASIBLE: the solver instantiation with the rule (never with xi: check_detect_flags)
+  const bool di = solver && !xi && (args.flags & SOCP_F_DETECT_INFEASIBLE) != 0;
+  int kind = qp   ? (solver ? KIND_QP : KIND_QP_KKT)  // (the plugin modes: the QP plugin-entry kernel)
+             : di ? KIND_DI
+             : xi ? (solver ? KIND_XI : KIND_XI_KKT)
+                  : (solver ? KIND_SOLVE : KIND_KKT);
+  // the slot plan: the plain solver only -- the kernel compiled for the table's pair of pure slots (the plugin
+  // entries keep their records' layout; the xi and di solvers keep their one kernel; the QP solver is mixed only)
+  const bool plain = kind == KIND_SOLVE;
+  args.slot_rot = args.slot_kinds = 0;
+  if (plain) {
+    int32_t rot = 0, kinds = 0;
+    small_slot_plan(args.cones, args.nc, args.k, args.al_rows, env_enabled("SOCP_SLOT_SPECIALISE"), rot, kinds);
+    const int pair = slot_pair_of(kinds & 15, kinds >> 4);
+    if (pair != SLOT_PAIR_NONE && v->k[KIND_SLOT_SP + pair - 1].fn) {
+      kind = KIND_SLOT_SP + pair - 1;
+      args.slot_rot = rot;
+      args.slot_kinds = kinds;
+      // the same solver compiled for exactly this launch's dims, cone table, al_rows, slot_rot and fuse_u,
+      // where there is one (small_exact_fit: SOCP_FUSE_U=0 or SOCP_SLOT_SPECIALISE=0 so leave none)
+      if (v->k[KIND_EXACT_SP + pair - 1].fn && env_enabled("SOCP_EXACT_FIT") &&
+          small_exact_fit(args, v->NQ, v->NP, v->MQ, pair))
+        kind = KIND_EXACT_SP + pair - 1;
+    }
+  }
+  if (!v->k[kind].fn) return fail(SOCP_E_UNSUPPORTED, "no compiled kernel for these flags");
+  // the load forms the initial point's G'G: the plain solver kernels compiled with the pipelined
+  // load (mixed or pure-slot), when an initial factorisation follows the load (no warm start)
+  args.init_overlap = plain && init_overlap_kernel(v->NQ, v->NP, v->MQ, 0) && !(args.flags & SOCP_F_WARM_START) &&
+                      env_enabled("SOCP_INIT_OVERLAP");
+  *out = v->k[kind];
+  return 0;
 }
 
 extern "C" int socp_debug_exact_fit(const socp_dims* d, const int32_t* kind, const int32_t* offs, const int32_t* dim,
                                     int32_t flags, int32_t* exact) {
-  ConeTable tab;
+  SmallArgs a{};
   int deg = 0;
   if (!exact) return fail(SOCP_E_INVALID, "output pointer is NULL");
-  {
-    const int rc = check_problem(d, kind, offs, dim, &tab, &deg);
-    if (rc) return rc;
-  }
+  TRY(check_problem(d, kind, offs, dim, &a.cones, &deg));
   *exact = 0;
-  const SmallVariant* v = pick_variant(d->n, d->m, d->k);
-  if (!v || d->ncones > NCS || (flags & SOCP_F_FORCE_LARGE)) return 0;  // the blocked kernel's
-  // (the xi and di solvers keep their one kernel; the rest is what launch_small sets for a plain solve)
-  if (flags & (SOCP_F_EXPLICIT_INVERSE | SOCP_F_DETECT_INFEASIBLE)) return 0;
-  SmallArgs a{};
-  a.n = d->n;
-  a.m = d->m;
-  a.k = d->k;
-  a.nc = tab.nc;
-  a.cones = tab;
-  small_cone_geometry(a, v);
-  small_slot_plan(a.cones, a.nc, a.k, a.al_rows, env_enabled("SOCP_SLOT_SPECIALISE"), a.slot_rot, a.slot_kinds);
-  *exact = small_exact_pair(a, v) != SLOT_PAIR_NONE ? 1 : 0;
+  const SmallVariant* v = nullptr;
+  if (!engine_fits(*d, flags, KIND_SOLVE, &v) || !v) return 0;  // the blocked kernel's, or no kernel's
+  // what socp_batch_solve_ex gives launch_small of the choice's inputs
+  fill_args(a, *d, d->batch, deg, nullptr);
+  a.mode = MODE_SOLVE;
+  a.flags = flags & ~SOCP_F_EQUILIBRATE;
+  SmallKernel kern;
+  TRY(small_select(v, a, false, &kern));
+  for (int pair = SLOT_PAIR_SP; pair <= SLOT_PAIR_PP; ++pair)
+    if (kern.fn == v->k[KIND_EXACT_SP + pair - 1].fn) *exact = 1;
+  return 0;
+}
+
+// a persistent kernel's launch: its problem counter zeroed, the launch inside the next timing pair, its name kept
+static int launch_counted(socp_ctx* ctx, const SmallKernel& sel, int64_t grid, int threads, size_t lds,
+                          int32_t* counter, void* args) {
+  HIPCHK(hipMemsetAsync(counter, 0, sizeof(int32_t), ctx->stream));
+  void* kargs[] = {args};
+  HIPCHK(timing_begin(ctx));
+  HIPCHK(hipLaunchKernel(sel.fn, dim3((unsigned)grid), dim3(threads), kargs, lds, ctx->stream));
+  HIPCHK(timing_end(ctx));
+  ctx->last_name = sel.name;
   return 0;
 }
 
 int host::launch_small(socp_ctx* ctx, SmallArgs& args, const SmallVariant* v, bool qp) {
-  small_cone_geometry(args, v);
   size_t lds = small_lds_bytes(v->NQ, v->NP, v->MQ);
   if (lds > 160 * 1024) return fail(SOCP_E_UNSUPPORTED, "LDS footprint too large");
-  const bool solver = args.mode == MODE_SOLVE;
-  // SOCP_F_EXPLICIT_INVERSE: the explicit-inverse variants (m <= 16 shapes; larger m form Li anyway)
-  const bool xi = (args.flags & SOCP_F_EXPLICIT_INVERSE) != 0 && v->xi_kernel;
-  // SOCP_F_DETECT_INFEASIBLE: the solver instantiation with the rule (never with xi: check_detect_flags)
-  const bool di = solver && !xi && (args.flags & SOCP_F_DETECT_INFEASIBLE) != 0;
-  // qp: the QP solver, or (the plugin modes) the QP plugin-entry kernel
-  const void* kern = qp   ? (solver ? v->qp_kernel : v->qp_kkt_kernel)
-                     : di ? v->di_kernel
-                     : xi ? (solver ? v->xi_kernel : v->xi_kkt_kernel)
-                          : (solver ? v->kernel : v->kkt_kernel);
-  // the slot plan: the plain solver only -- the kernel compiled for the table's pair of pure slots
-  // (the plugin entries keep their records' layout; the xi and di solvers keep their one kernel)
-  args.slot_rot = args.slot_kinds = 0;
-  if (solver && !xi && !di && !qp) {  // (the QP solver is compiled for mixed slots only)
-    int32_t rot = 0, kinds = 0;
-    small_slot_plan(args.cones, args.nc, args.k, args.al_rows, env_enabled("SOCP_SLOT_SPECIALISE"), rot, kinds);
-    const int pair = slot_pair_of(kinds & 15, kinds >> 4);
-    if (pair != SLOT_PAIR_NONE && v->slot_kernel[pair - 1]) {
-      kern = v->slot_kernel[pair - 1];
-      args.slot_rot = rot;
-      args.slot_kinds = kinds;
-      // the same solver compiled for exactly this launch's geometry, where there is one
-      const int ex = small_exact_pair(args, v);
-      if (ex != SLOT_PAIR_NONE) kern = v->exact_kernel[ex - 1];
-    }
-  }
-  if (!kern) return fail(SOCP_E_UNSUPPORTED, "no compiled kernel for these flags");
-  // the load forms the initial point's G'G: the plain solver kernels compiled with the pipelined
-  // load (mixed or pure-slot), when an initial factorisation follows the load (no warm start)
-  args.init_overlap = solver && !xi && !di && !qp && init_overlap_kernel(v->NQ, v->NP, v->MQ, 0) &&
-                      !(args.flags & SOCP_F_WARM_START) && env_enabled("SOCP_INIT_OVERLAP");
+  SmallKernel sel;
+  TRY(small_select(v, args, qp, &sel));
   if (lds > 64 * 1024)
-    HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(hipFuncSetAttribute(sel.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   int per_cu = 0;
-  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64, lds));
+  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sel.fn, 64, lds));
   if (per_cu < 1) per_cu = 1;
   int64_t blocks = (int64_t)ctx->num_cu * per_cu;
   if (blocks > args.B) blocks = args.B;
   if (blocks < 1) blocks = 1;
-  HIPCHK(hipMemsetAsync(args.counter, 0, sizeof(int32_t), ctx->stream));
   args.stamps = g_stamps;
-  void* kargs[] = {&args};
-  HIPCHK(timing_begin(ctx));
-  HIPCHK(hipLaunchKernel(kern, dim3((unsigned)blocks), dim3(64), kargs, lds, ctx->stream));
-  HIPCHK(timing_end(ctx));
-  ctx->last_name = qp   ? (solver ? v->qp_name : v->qp_kkt_name)
-                   : di ? v->di_name
-                   : xi ? (solver ? v->xi_name : v->xi_kkt_name)
-                        : (solver ? v->name : v->kkt_name);
-  return 0;
+  return launch_counted(ctx, sel, blocks, 64, lds, args.counter, &args);
 }
 
 int host::launch_large(socp_ctx* ctx, const SmallArgs& a, double* rec, bool qp) {
@@ -435,11 +447,11 @@ int host::launch_large(socp_ctx* ctx, const SmallArgs& a, double* rec, bool qp) 
   const bool xi = (a.flags & SOCP_F_EXPLICIT_INVERSE) != 0;
   if (!large_fits(a.n, a.m, a.k, a.nc, &lds, &gv)) return fail(SOCP_E_UNSUPPORTED, kUnsupported);
   const bool di = a.mode == MODE_SOLVE && !xi && (a.flags & SOCP_F_DETECT_INFEASIBLE) != 0;
-  const void* kern = large_kernel_ptr(xi, gv, di, qp);
-  if (!kern) return fail(SOCP_E_UNSUPPORTED, "no compiled kernel for these flags");
-  HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const LargeKernel sel = large_kernel(xi, gv, di, qp);
+  if (!sel.fn) return fail(SOCP_E_UNSUPPORTED, "no compiled kernel for these flags");
+  HIPCHK(hipFuncSetAttribute(sel.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   int per_cu = 0;
-  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 512, lds));
+  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sel.fn, 512, lds));
   if (per_cu < 1) return fail(SOCP_E_UNSUPPORTED, "blocked kernel does not fit on a CU");
   int64_t grid = (int64_t)ctx->num_cu * per_cu;
   if (grid > a.B) grid = a.B;
@@ -453,13 +465,7 @@ int host::launch_large(socp_ctx* ctx, const SmallArgs& a, double* rec, bool qp) 
   if (rc) return fail(rc, "workspace allocation failed");
   la.ws = (double*)ctx->buf[socp_ctx::B_LWS].p;
   la.rec = rec;
-  HIPCHK(hipMemsetAsync(a.counter, 0, sizeof(int32_t), ctx->stream));
-  void* kargs[] = {&la};
-  HIPCHK(timing_begin(ctx));
-  HIPCHK(hipLaunchKernel(kern, dim3((unsigned)grid), dim3(512), kargs, lds, ctx->stream));
-  HIPCHK(timing_end(ctx));
-  ctx->last_name = large_kernel_name(xi, gv, di, qp);
-  return 0;
+  return launch_counted(ctx, sel, grid, 512, lds, a.counter, &la);
 }
 
 socp_params host::params_or_default(const socp_params* params) {
@@ -699,14 +705,7 @@ static int batch_solve_impl(socp_ctx* ctx, const socp_dims* dims, const int32_t*
   const int n = dims->n, m = dims->m, k = dims->k;
   TRY(check_detect_flags(P.flags));
   const bool qp = Pm != nullptr;
-  if (qp && (P.flags & SOCP_F_EXPLICIT_INVERSE))
-    return fail(SOCP_E_UNSUPPORTED,
-                "socp_batch_solve_qp with SOCP_F_EXPLICIT_INVERSE: no QP kernel is compiled in the explicit-inverse "
-                "operation order");
-  if (qp && (P.flags & SOCP_F_DETECT_INFEASIBLE))
-    return fail(SOCP_E_UNSUPPORTED,
-                "socp_batch_solve_qp with SOCP_F_DETECT_INFEASIBLE: the unboundedness rule would also need Px = 0, "
-                "which the detecting kernels do not test");
+  if (qp) TRY(check_qp_flags(P.flags, "socp_batch_solve_qp"));
   const bool eq = (P.flags & SOCP_F_EQUILIBRATE) != 0;
   if (eq && (P.flags & SOCP_F_WARM_START))
     return fail(SOCP_E_UNSUPPORTED,
@@ -718,11 +717,8 @@ static int batch_solve_impl(socp_ctx* ctx, const socp_dims* dims, const int32_t*
   if (B == 0) return 0;
   if (!c || !G || !h || !x || !z || !s || !iters || !status || (m > 0 && (!A || !b || !y)))
     return fail(SOCP_E_INVALID, "NULL data pointer");
-  const bool force_large = (P.flags & SOCP_F_FORCE_LARGE) != 0;
-  const SmallVariant* v = (force_large || dims->ncones > NCS) ? nullptr : pick_variant(n, m, k);
-  if (qp && v && !v->qp_kernel) v = nullptr;  // no QP instantiation of the shape: the blocked kernel
-  if (!v && !large_fits(n, m, k, dims->ncones, nullptr))
-    return fail(SOCP_E_UNSUPPORTED, kUnsupported);
+  const SmallVariant* v = nullptr;
+  TRY(choose_engine(*dims, P.flags, qp ? KIND_QP : KIND_SOLVE, &v));
   HIPCHK(hipSetDevice(ctx->device));
   const bool dev = (P.flags & SOCP_F_DEVICE_PTRS) != 0;
   const Stager st{ctx->buf, ctx->stream, dev, nullptr};
@@ -860,10 +856,8 @@ static int batch_kkt_impl(socp_ctx* ctx, const socp_dims* dims, const int32_t* c
                           int32_t* kkt_status, int32_t flags) {
   if (!ctx) return fail(SOCP_E_INVALID, "ctx is NULL");
   const bool qp = Pm != nullptr;
-  if (qp && (flags & SOCP_F_EXPLICIT_INVERSE))
-    return fail(SOCP_E_UNSUPPORTED,
-                "socp_batch_kkt_solve_qp with SOCP_F_EXPLICIT_INVERSE: no QP kernel is compiled in the "
-                "explicit-inverse operation order");
+  // (SOCP_F_DETECT_INFEASIBLE is no flag of the plugin entries: ignored, as socp_batch_kkt_solve ignores it)
+  if (qp) TRY(check_qp_flags(flags & ~SOCP_F_DETECT_INFEASIBLE, "socp_batch_kkt_solve_qp"));
   SmallArgs a;
   memset(&a, 0, sizeof(a));
   int degree = 0;
@@ -874,11 +868,8 @@ static int batch_kkt_impl(socp_ctx* ctx, const socp_dims* dims, const int32_t* c
   if (!G || !s || !z || !dx || !dz || !ds || !cx || !cz || !cs || !kkt_status ||
       (m > 0 && (!A || !dy || !cy)))
     return fail(SOCP_E_INVALID, "NULL data pointer");
-  const bool force_large = (flags & SOCP_F_FORCE_LARGE) != 0;
-  const SmallVariant* v = (force_large || dims->ncones > NCS) ? nullptr : pick_variant(n, m, k);
-  if (qp && v && !v->qp_kkt_kernel) v = nullptr;  // no QP instantiation of the shape: the blocked kernel
-  if (!v && !large_fits(n, m, k, dims->ncones, nullptr))
-    return fail(SOCP_E_UNSUPPORTED, kUnsupported);
+  const SmallVariant* v = nullptr;
+  TRY(choose_engine(*dims, flags, qp ? KIND_QP_KKT : KIND_KKT, &v));
   HIPCHK(hipSetDevice(ctx->device));
   const bool dev = (flags & SOCP_F_DEVICE_PTRS) != 0;
   const Stager st{ctx->buf, ctx->stream, dev, nullptr};

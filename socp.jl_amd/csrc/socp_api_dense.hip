@@ -33,10 +33,8 @@ static int dense_create_impl(socp_ctx* ctx, const socp_dims* dims, const int32_t
   *out = nullptr;
   if (!ctx) return fail(SOCP_E_INVALID, "ctx is NULL");
   const bool qp = Pm != nullptr;
-  if (qp && (flags & SOCP_F_EXPLICIT_INVERSE))
-    return fail(SOCP_E_UNSUPPORTED,
-                "socp_dense_create_qp with SOCP_F_EXPLICIT_INVERSE: no QP kernel is compiled in the explicit-inverse "
-                "operation order");
+  // (SOCP_F_DETECT_INFEASIBLE is no flag of the plugin entries: ignored, as socp_dense_create ignores it)
+  if (qp) TRY(check_qp_flags(flags & ~SOCP_F_DETECT_INFEASIBLE, "socp_dense_create_qp"));
   socp_dense* h = new socp_dense();
   h->ctx = ctx;
   SmallArgs& a = h->a;
@@ -51,12 +49,8 @@ static int dense_create_impl(socp_ctx* ctx, const socp_dims* dims, const int32_t
   const int64_t B = dims->batch;
   const int n = dims->n, m = dims->m, k = dims->k;
   if (B > 0 && (!G || (m > 0 && !A))) return bail(fail(SOCP_E_INVALID, "NULL data pointer"));
-  const bool force_large = (flags & SOCP_F_FORCE_LARGE) != 0;
-  h->v = (force_large || dims->ncones > NCS) ? nullptr : pick_variant(n, m, k);
-  if (qp && h->v && !h->v->qp_kkt_kernel) h->v = nullptr;  // no QP instantiation of the shape: the blocked kernel
   h->qp = qp;
-  if (!h->v && !large_fits(n, m, k, dims->ncones, nullptr))
-    return bail(fail(SOCP_E_UNSUPPORTED, kUnsupported));
+  if ((rc = choose_engine(*dims, flags, qp ? KIND_QP_KKT : KIND_KKT, &h->v))) return bail(rc);
   if (hipSetDevice(ctx->device) != hipSuccess) return bail(fail(SOCP_E_HIP, "hipSetDevice"));
   const bool dev = (flags & SOCP_F_DEVICE_PTRS) != 0;
   fill_args(a, *dims, B, degree, &kKktParams);

@@ -161,8 +161,7 @@ extern "C" int socp_ingest_create(socp_ctx* ctx, const socp_dims* dims, const in
   g->flags = flags & SOCP_F_FORCE_LARGE;
   g->shared = (flags & SOCP_F_SHARED_MATRICES) != 0;
   const int n = dims->n, m = dims->m, k = dims->k;
-  g->v = ((flags & SOCP_F_FORCE_LARGE) || dims->ncones > NCS) ? nullptr : pick_variant(n, m, k);
-  if (!g->v && !large_fits(n, m, k, dims->ncones, nullptr)) return bail(fail(SOCP_E_UNSUPPORTED, kUnsupported));
+  if ((rc = choose_engine(*dims, flags, KIND_SOLVE, &g->v))) return bail(rc);
   hipError_t e;
   if ((e = hipSetDevice(ctx->device)) != hipSuccess) return bail(fail(SOCP_E_HIP, "hipSetDevice"));
   if ((e = hipStreamCreateWithFlags(&g->h2d, hipStreamNonBlocking)) != hipSuccess ||
@@ -320,7 +319,8 @@ static int ingest_solve(socp_ingest* g, IngestSlot& sl, int64_t B, const uint8_t
   a.counter = (int32_t*)g->counter.p;
   const bool qp = P_dev != nullptr;
   if (qp) small_set_qp(a, P_dev);
-  const SmallVariant* v = (qp && g->v && !g->v->qp_kernel) ? nullptr : g->v;  // (as batch_solve_impl)
+  const SmallVariant* v = g->v;  // create's choice; a submit with P asks again for the QP solver (as batch_solve_impl)
+  if (qp) TRY(choose_engine(d, g->flags, KIND_QP, &v));
   HIPCHK(hipStreamWaitEvent(ctx->stream, sl.ready, 0));
   TRY(v ? launch_small(ctx, a, v, qp) : launch_large(ctx, a, nullptr, qp));
   HIPCHK(hipEventRecord(sl.solved, ctx->stream));
@@ -356,14 +356,7 @@ static int ingest_submit_impl(socp_ingest* g, bool qp_entry, int64_t batch, cons
     return fail(SOCP_E_INVALID, "shared ingest: socp_ingest_set_matrices_qp has not given a P");
   const bool qp = qp_entry && g && (g->shared || Pm);
   // the synchronous entry's refusals, before the slot is claimed
-  if (qp && params && (params->flags & SOCP_F_EXPLICIT_INVERSE))
-    return fail(SOCP_E_UNSUPPORTED,
-                "socp_ingest_submit_qp with SOCP_F_EXPLICIT_INVERSE: no QP kernel is compiled in the explicit-inverse "
-                "operation order");
-  if (qp && params && (params->flags & SOCP_F_DETECT_INFEASIBLE))
-    return fail(SOCP_E_UNSUPPORTED,
-                "socp_ingest_submit_qp with SOCP_F_DETECT_INFEASIBLE: the unboundedness rule would also need Px = 0, "
-                "which the detecting kernels do not test");
+  if (qp && params) TRY(check_qp_flags(params->flags, "socp_ingest_submit_qp"));
   if (qp && !g->shared) TRY(ingest_ensure_P(g));
   IngestSlot* slp = nullptr;
   TRY(ingest_begin(g, batch, &slp));

@@ -135,9 +135,10 @@ int check_problem(const socp_dims* d, const int32_t* kind, const int32_t* offs, 
                   int* degree);
 int check_detect_flags(int32_t flags);
 int check_no_equilibrate(int32_t flags, const char* who);
-const SmallVariant* pick_variant(int n, int m, int k);
-bool large_fits(int n, int m, int k, int nc, size_t* lds_bytes, bool* gv = nullptr);
+int check_qp_flags(int32_t flags, const char* who);
 extern const char* const kUnsupported;
+// the engine of a call that wants kernel `kind`: *v the register kernel's variant, or NULL for the blocked kernel
+int choose_engine(const socp_dims& d, int32_t flags, SmallKind kind, const SmallVariant** v);
 
 // ---------------------------------------------------------------- launch
 // *params, or socp_params_default's values when it is NULL
@@ -149,6 +150,8 @@ socp_params fill_args(SmallArgs& a, const socp_dims& d, int64_t B, int degree, c
 constexpr socp_params kKktParams = {1, 3, 0.0, 0.0, 0.0, 0, 0};
 // a.c | a.b | a.h as one zeroed block in `buf`: the KKT entries do not use them but the loader reads them
 int zero_cbh(DevBuf& buf, hipStream_t stream, SmallArgs& a);
+// the kernel of variant v that a launch of args runs (no HIP call: socp_debug_exact_fit asks it too)
+int small_select(const SmallVariant* v, SmallArgs& args, bool qp, SmallKernel* out);
 // qp: the QP solver (socp_batch_solve_qp; args carries P, small_set_qp)
 int launch_small(socp_ctx* ctx, SmallArgs& args, const SmallVariant* v, bool qp = false);
 int launch_large(socp_ctx* ctx, const SmallArgs& a, double* rec = nullptr, bool qp = false);

@@ -11,33 +11,35 @@
 
 namespace socp {
 
+// The kernel kinds of a variant, one per record of gen_inst.py's KINDS and in its order (inst_table.hip
+// asserts both, and that socp_small.hpp's small_km() decodes each kind's KM to what the record states).
+// host::small_select (socp_api.hip) is the one place that chooses among them.
+enum SmallKind {
+  KIND_SOLVE,  // KM 0: MODE_SOLVE
+  KIND_KKT,    // KM 1: MODE_KKT / MODE_SETUP / MODE_SOLVEKKT
+  // SOCP_F_EXPLICIT_INVERSE (KM 2 / 3): the same two with Li = H^-1 formed from
+  // the Cholesky factor; absent where the shape forms it anyway (m > 16)
+  KIND_XI, KIND_XI_KKT,
+  KIND_DI,  // KM 4: the solver with SOCP_F_DETECT_INFEASIBLE's rule
+  // the plain solver compiled for pure slots (KM = SLOT_PAIR_* << 4; two-slot
+  // shapes, NP > 16): KIND_SLOT_SP + SLOT_PAIR_* - 1
+  KIND_SLOT_SP, KIND_SLOT_PS, KIND_SLOT_SS, KIND_SLOT_PP,
+  KIND_QP,      // KM 8: socp_batch_solve_qp, the solver with the quadratic term P, mixed slots
+  KIND_QP_KKT,  // KM 9: socp_batch_kkt_solve_qp / socp_dense_create_qp, the plugin-entry kernel with P in H
+  // the pair's plain solver compiled for one exact launch geometry (KM = (pair << 4) | KM_EXACT,
+  // socp_small.hpp ExactFit): KIND_EXACT_SP + SLOT_PAIR_* - 1
+  KIND_EXACT_SP, KIND_EXACT_PS, KIND_EXACT_SS, KIND_EXACT_PP,
+  SMALL_KIND_COUNT
+};
+// a compiled kernel and what socp_last_kernel_name calls it; {NULL, NULL}: not compiled
+struct SmallKernel {
+  const void* fn;
+  const char* name;
+};
+typedef SmallKernel LargeKernel;
 struct SmallVariant {
   int NQ, NP, MQ;
-  const void* kernel;  // socp_small_kernel<NQ,NP,MQ,0>: MODE_SOLVE
-  const char* name;
-  const void* kkt_kernel;  // socp_small_kernel<NQ,NP,MQ,1>: MODE_KKT / MODE_SETUP / MODE_SOLVEKKT
-  const char* kkt_name;
-  // SOCP_F_EXPLICIT_INVERSE (KM 2 / 3): the same two with Li = H^-1 formed
-  // from the Cholesky factor; NULL where the shape forms it anyway (m > 16)
-  const void* xi_kernel;
-  const char* xi_name;
-  const void* xi_kkt_kernel;
-  const char* xi_kkt_name;
-  // SOCP_F_DETECT_INFEASIBLE (KM 4): the solver with the infeasibility rule
-  const void* di_kernel;
-  const char* di_name;
-  // the plain solver compiled for pure slots (KM = SLOT_PAIR_* << 4; two-slot
-  // shapes, NP > 16, else NULL): [SLOT_PAIR_* - 1]
-  const void* slot_kernel[4];
-  // socp_batch_solve_qp (KM 8): the solver with the quadratic term P, mixed slots
-  const void* qp_kernel;
-  const char* qp_name;
-  // the pair's plain solver compiled for one exact launch geometry (KM = (pair << 4) | KM_EXACT,
-  // socp_small.hpp ExactFit; gen_inst.py EXACT), else NULL: [SLOT_PAIR_* - 1]
-  const void* exact_kernel[4];
-  // socp_batch_kkt_solve_qp / socp_dense_create_qp (KM 9): the plugin-entry kernel with P in H
-  const void* qp_kkt_kernel;
-  const char* qp_kkt_name;
+  SmallKernel k[SMALL_KIND_COUNT];  // by SmallKind
 };
 
 // table of compiled register-resident variants, ordered by (NQ, NP, MQ)
@@ -132,7 +134,7 @@ struct LargeArgs {
 // di: the solver with the infeasibility rule (SOCP_F_DETECT_INFEASIBLE; not with xi)
 // qp: the kernels with the quadratic term P (socp_batch_solve_qp, and the QP plugin
 // entries in MODE_KKT / MODE_SETUP / MODE_SOLVEKKT; with neither xi nor di)
-const void* large_kernel_ptr(bool xi, bool gv, bool di = false, bool qp = false);
-const char* large_kernel_name(bool xi, bool gv, bool di = false, bool qp = false);
+// {NULL, NULL}: no such kernel is compiled
+LargeKernel large_kernel(bool xi, bool gv, bool di, bool qp);
 
 }  // namespace socp

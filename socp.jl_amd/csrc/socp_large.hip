@@ -2789,22 +2789,26 @@ extern template __global__ void socp_large_kernel<false, false, false, true>(Lar
 extern template __global__ void socp_large_kernel<false, true, false, true>(LargeArgs);
 }  // namespace lg
 
-const void* large_kernel_ptr(bool xi, bool gv, bool di, bool qp) {
-  if (qp)
-    return (xi || di) ? nullptr
-                      : (gv ? (const void*)&lg::socp_large_kernel<false, true, false, true>
-                            : (const void*)&lg::socp_large_kernel<false, false, false, true>);
-  if (di && !xi)
-    return gv ? (const void*)&lg::socp_large_kernel<false, true, true>
-              : (const void*)&lg::socp_large_kernel<false, false, true>;
-  if (gv) return xi ? (const void*)&lg::socp_large_kernel<true, true> : (const void*)&lg::socp_large_kernel<false, true>;
-  return xi ? (const void*)&lg::socp_large_kernel<true, false> : (const void*)&lg::socp_large_kernel<false, false>;
-}
-const char* large_kernel_name(bool xi, bool gv, bool di, bool qp) {
-  if (qp) return gv ? "socp_large_qp_gv_kernel" : "socp_large_qp_kernel";
-  if (di && !xi) return gv ? "socp_large_di_gv_kernel" : "socp_large_di_kernel";
-  if (gv) return xi ? "socp_large_xi_gv_kernel" : "socp_large_gv_kernel";
-  return xi ? "socp_large_xi_kernel" : "socp_large_kernel";
+// the eight compiled kernels: every other (xi, gv, di, qp) has none
+LargeKernel large_kernel(bool xi, bool gv, bool di, bool qp) {
+#define LG_KERNEL(xi, gv, di, qp, name) {xi, gv, di, qp, {(const void*)&lg::socp_large_kernel<xi, gv, di, qp>, name}}
+  static const struct {
+    bool xi, gv, di, qp;
+    LargeKernel k;
+  } kernels[] = {
+      LG_KERNEL(false, true, false, true, "socp_large_qp_gv_kernel"),
+      LG_KERNEL(false, false, false, true, "socp_large_qp_kernel"),
+      LG_KERNEL(false, true, true, false, "socp_large_di_gv_kernel"),
+      LG_KERNEL(false, false, true, false, "socp_large_di_kernel"),
+      LG_KERNEL(true, true, false, false, "socp_large_xi_gv_kernel"),
+      LG_KERNEL(false, true, false, false, "socp_large_gv_kernel"),
+      LG_KERNEL(true, false, false, false, "socp_large_xi_kernel"),
+      LG_KERNEL(false, false, false, false, "socp_large_kernel"),
+  };
+#undef LG_KERNEL
+  for (const auto& e : kernels)
+    if (e.xi == xi && e.gv == gv && e.di == di && e.qp == qp) return e.k;
+  return {nullptr, nullptr};
 }
 #endif
 

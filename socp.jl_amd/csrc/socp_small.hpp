@@ -201,6 +201,21 @@ inline bool small_exact_fit(const SmallArgs& a, int NQ, int NP, int MQ, int pair
   return true;
 }
 
+// socp_small_kernel's fourth template argument KM, decoded in this one place (the kernel's own template
+// arguments read it, and inst_table.hip's static_asserts hold it to gen_inst.py's KINDS).  bit 0 plugin: the
+// plugin-entry kernel (MODE_KKT / MODE_SETUP / MODE_SOLVEKKT) instead of the solver; bit 1 xi: the explicit-inverse
+// variant; bit 2 di: the solver with SOCP_F_DETECT_INFEASIBLE; bit 3 qp: the QP solver (socp_batch_solve_qp; mixed
+// slots only), with bit 0 the QP plugin entries; bits 4..6 pair: the plain solver for a pair of pure slots
+// (SLOT_PAIR_*); bit 7 exact (KM_EXACT, with a pair): that solver at one exact launch geometry (ExactFit)
+struct SmallKM {
+  bool plugin, xi, di, qp;
+  int pair;
+  bool exact;
+};
+constexpr SmallKM small_km(int KM) {
+  return {(KM & 1) != 0, (KM & 2) != 0, (KM & 4) != 0, (KM & 8) != 0, (KM >> 4) & 7, (KM & KM_EXACT) != 0};
+}
+
 // MODE_SOLVE reads no right-hand side: with F_DETECT the slot of dx carries
 // the bits of the infeasibility tolerance, so that the layout of the kernel
 // arguments -- and with it the code of every kernel that does not detect --
@@ -775,7 +790,8 @@ enum : int { FAC_SCALED, FAC_IDENT, FAC_SCALED_U, FAC_IDENT_H };
 // kernels) of C2's variant.  Every other instantiation keeps load_problem and
 // factor() as they were, at compile time.
 constexpr bool init_overlap_kernel(int NQ, int NP, int MQ, int KM) {
-  return NQ == 4 && NP == 24 && MQ == 1 && (KM & 15) == 0;
+  const SmallKM K = small_km(KM);
+  return NQ == 4 && NP == 24 && MQ == 1 && !K.plugin && !K.xi && !K.di && !K.qp;
 }
 // driver micro-phases and solve kinds
 enum : int {
@@ -4036,21 +4052,15 @@ struct Small {
   }
 };
 
-// KM bits 4..: the pure-slot solver kernels (KM = SLOT_PAIR_* << 4, plain solver only);
-// KM bit 0: the plugin-entry kernel (MODE_KKT / MODE_SETUP / MODE_SOLVEKKT)
-// instead of the solver; bit 1: the explicit-inverse variant (XI above);
-// bit 2 (KM = 4): the solver with SOCP_F_DETECT_INFEASIBLE;
-// bit 3 (KM = 8): the QP solver (socp_batch_solve_qp), mixed slots only; with bit 0
-// (KM = 9) the QP plugin entries (socp_batch_kkt_solve_qp, socp_dense_create_qp);
-// bit 7 (KM_EXACT, with a pair): the pair's plain solver at one exact launch geometry (ExactFit)
+// KM: the kernel's kind, small_km() above
 template <int NQ, int NP, int MQ, int KM>
 #ifndef SOCP_DEV_MINW
 #define SOCP_DEV_MINW 1  // probe builds only: waves per SIMD the register allocation must allow
 #endif
-__global__ void __launch_bounds__(64, (KM & 3) == 0 ? SOCP_DEV_MINW : 1) socp_small_kernel(SmallArgs args) {
-  Small<NQ, NP, MQ, (KM & 2) != 0, slot_pair_kind((KM >> 4) & 7, 0), slot_pair_kind((KM >> 4) & 7, 1), (KM & 8) != 0,
-        (KM & KM_EXACT) != 0>
-      S(args);
+__global__ void __launch_bounds__(64, !small_km(KM).plugin && !small_km(KM).xi ? SOCP_DEV_MINW : 1)
+    socp_small_kernel(SmallArgs args) {
+  constexpr SmallKM K = small_km(KM);
+  Small<NQ, NP, MQ, K.xi, slot_pair_kind(K.pair, 0), slot_pair_kind(K.pair, 1), K.qp, K.exact> S(args);
   S.init_tables();
   STAMP_START_S(S);
   while (true) {
@@ -4063,7 +4073,7 @@ __global__ void __launch_bounds__(64, (KM & 3) == 0 ? SOCP_DEV_MINW : 1) socp_sm
       S.template run<0, false, true>(p, h_formed);
     } else {
       S.load_problem(p);
-      S.template run<KM & 1, (KM & 4) != 0>(p);
+      S.template run<K.plugin, K.di>(p);
     }
   }
   S.flush_stamps();
