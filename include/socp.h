@@ -350,6 +350,83 @@ int socp_batch_kkt_solve_qp(socp_ctx* ctx, const socp_dims* dims,
                             double* cx, double* cy, double* cz, double* cs,
                             int32_t* kkt_status, int32_t flags);
 
+/* Differentiable solves (the reference has none).  The gradient
+ * of a solve is the adjoint of the block system above -- exactly so at a point
+ * of the central path (s o z = mu e), which a solver's returned iterate is not:
+ * Mehrotra steps of length 0.99 leave it off-centre by its own size.  So there
+ * are two entries: one centres an iterate, one forms the adjoint at a point.
+ *
+ * socp_batch_centre: `steps` (0..16) pure Newton centring passes on (x, y, z, s),
+ * in place.  Each pass, per problem:
+ *   1. mu = s'z / deg, deg = POC rows + SOC cones;
+ *   2. lam = compute_scaling's l at (s, z) (scalings.jl:22-99; IEEE sqrt and /);
+ *   3. dx = -(Px + c + A'y + G'z), dy = -(Ax - b), dz = -(Gx + s - h),
+ *      ds = mu e - lam o lam   (no Mehrotra term; the residuals stay in);
+ *   4. one socp_batch_kkt_solve_qp at (s, z) on that right-hand side (P == NULL:
+ *      socp_batch_kkt_solve's kernels), chosen and launched as a caller's own;
+ *   5. t = 1, halved while z + t cz or s + t cs is not interior (POC entries
+ *      > 0, SOC v0 > sqrt(sum_{i>=1} v_i^2)), given up below 2^-30;
+ *   6. (x, y, z, s) += t (cx, cy, cz, cs).
+ * The last pass refines its step once before 5: the residual of the three
+ * linear rows at (cx, cy, cz, cs), with ds = 0, goes through the same entry
+ * again and the result is added.  The kernels' solve leaves those rows a
+ * residual of its own accuracy times the step (1e-12 .. 1e-9 on ill-conditioned
+ * late iterates); with the refinement the returned point satisfies
+ * Px + c + A'y + G'z = 0, Ax = b, Gx + s = h to the rounding of their terms.
+ * So `steps` passes cost steps + 1 KKT solves.
+ * status[p]: 0; the KKT solve's status; or SOCP_DOMAIN_ERROR where no t is
+ * found.  Such a problem stops at its last good iterate and the others go on.
+ * res (4 per problem, may be NULL): ||rd||_2, ||rp||_2, z's and the off-centre
+ * measure ||lam o lam - mu e||_2 / mu at the returned point.  steps = 0 returns
+ * the iterate's bits and its res.  P may be NULL; sing as in socp_batch_solve.
+ * For a `sing` problem dy = -rp != 0, where the sing formula is not the block
+ * system's solve (socp_batch_kkt_solve above: its cx leaves A cx - dy of dy's
+ * size); as in the solver that is harmless once rp is small, and it is left so.
+ * flags: SOCP_F_DEVICE_PTRS (stream-ordered, no synchronisation) |
+ * SOCP_F_FORCE_LARGE | SOCP_F_SHARED_MATRICES (one P, A, G and sing byte; the
+ * outputs are the bits of the replicated call).  SOCP_F_EXPLICIT_INVERSE
+ * returns SOCP_E_UNSUPPORTED, every other bit SOCP_E_INVALID. */
+int socp_batch_centre(socp_ctx* ctx, const socp_dims* dims,
+                      const int32_t* cone_kind, const int32_t* cone_offs, const int32_t* cone_dim,
+                      const double* P, const double* c, const double* A, const double* b,
+                      const double* G, const double* h, const uint8_t* sing,
+                      int32_t steps, int32_t flags,
+                      double* x, double* y, double* z, double* s,
+                      int32_t* status, double* res);
+
+/* The adjoint at a given point (x, y, z, s); no centring.  gx, gy, gz, gs are
+ * the upstream gradients dL/d(x, y, z, s), each may be NULL meaning zero.
+ * Definition:
+ *   Solve the block system of socp_batch_kkt_solve_qp at (s, z) with the
+ *   right-hand side (dx, dy, dz, ds) = (gx - G'gs, gy, gz, 0).  Call the
+ *   solution (ux, uy, uz, .) and set w = uz + gs.  Then
+ *     dc = -ux        db = uy         dh = w
+ *     dP = -(ux x' + x ux')/2
+ *     dA = -(y ux' + uy x')
+ *     dG = -(z ux' + w x')
+ * (the gs term uses row 3 of the system, ds = dh - dG x - G dx, so no scaling
+ * matrix is needed outside the KKT kernel).  Outputs, each may be NULL and is
+ * then skipped: dc[B n], db[B m], dh[B k]; dP[B n^2], dA[B m n], dG[B k n],
+ * column-major as the inputs; the adjoint variables ux[B n], uy[B m], uz[B k].
+ * skip (int32 per problem, may be NULL): a problem with skip[p] != 0, or whose
+ * KKT solve fails, gets zeros in every output -- never NaN, so that a sum over
+ * the batch stays finite -- and status[p] = skip[p], or else the KKT status.
+ * For a `sing` problem a nonzero gy is not supported: the sing formula is not
+ * the block system's solve when dy != 0.
+ * flags: SOCP_F_DEVICE_PTRS | SOCP_F_FORCE_LARGE; SOCP_F_SHARED_MATRICES (one
+ * P, A, G, sing) only while dP, dA and dG are NULL -- with one of them it
+ * returns SOCP_E_UNSUPPORTED (those are sums over the batch, not formed here);
+ * SOCP_F_EXPLICIT_INVERSE returns SOCP_E_UNSUPPORTED, every other bit
+ * SOCP_E_INVALID. */
+int socp_batch_vjp(socp_ctx* ctx, const socp_dims* dims,
+                   const int32_t* cone_kind, const int32_t* cone_offs, const int32_t* cone_dim,
+                   const double* P, const double* A, const double* G, const uint8_t* sing,
+                   const double* x, const double* y, const double* z, const double* s,
+                   const double* gx, const double* gy, const double* gz, const double* gs,
+                   const int32_t* skip, int32_t flags,
+                   double* dc, double* db, double* dh, double* dP, double* dA, double* dG,
+                   double* ux, double* uy, double* uz, int32_t* status);
+
 /* The same two methods split the way the reference's KKTSolver plugin is
  * (densesolver.jl): a handle stands for a batch of DenseSolver objects.
  *   socp_dense_create      replaces DenseSolver(...) construction

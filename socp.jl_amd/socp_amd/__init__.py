@@ -32,7 +32,7 @@ __all__ = [
     "POC", "SOC", "Problem", "State", "Scaling", "DenseSolver", "HipDenseSolver", "SolverState",
     "solve_socp", "solve_socp_batched", "compute_scaling", "setup_iter", "solve_kkt",
     "PosDefException", "DomainError", "batch_solve", "batch_kkt_solve", "DenseHandle", "Ingest",
-    "generate", "pack_csc", "equilibrate",
+    "generate", "pack_csc", "equilibrate", "batch_centre", "batch_vjp",
     "Context", "SocpError", "default_context", "cone_arrays",
     "CONVERGED", "MAXIT", "CHOL_H_FAILED", "CHOL_S_FAILED", "DOMAIN_ERROR",
     "PRIMAL_INFEASIBLE", "DUAL_INFEASIBLE",
@@ -375,6 +375,183 @@ def batch_kkt_solve(cones, n, m, k, A, G, sing, s, z, dx, dy, dz, ds, *, ctx=Non
         rc = L.socp_batch_kkt_solve_qp(ctx.handle, dims, p(kind), p(offs), p(dim), p(P), *tail)
     _lib.check(rc)
     return dict(cx=cx, cy=cy[:B * m], cz=cz, cs=cs, status=st)
+
+
+def _vjp_flags(dev, force_large, shared_matrices, explicit_inverse):
+    return ((F_DEVICE_PTRS if dev else 0) | (F_FORCE_LARGE if force_large else 0)
+            | (F_SHARED_MATRICES if shared_matrices else 0) | (F_EXPLICIT_INVERSE if explicit_inverse else 0))
+
+
+def _same_side(dev, G, **arrays):
+    """With torch inputs every array must be a contiguous tensor on G's device
+    (the library reads and writes them in place); with numpy inputs, none."""
+    for name, (a, dtype) in arrays.items():
+        if a is None:
+            continue
+        if not dev:
+            if _is_torch(a):
+                raise ValueError(f"{name} must be a host array, as G is")
+        elif not _is_torch(a) or str(a.dtype) != dtype or a.device != G.device or not a.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor on G's device")
+
+
+def batch_centre(cones, n, m, k, c, A, b, G, h, sing, x, y, z, s, *, steps=4, P=None, ctx=None, res=False,
+                 force_large=False, shared_matrices=False, explicit_inverse=False):
+    """Centre an iterate (socp_batch_centre): `steps` (0..16) pure Newton steps
+    towards s o z = mu e at the iterate's own mu = s'z / deg, each one fused
+    KKT solve and a full step, halved while it would leave the cone (the last
+    step is refined by a second solve, so that the point returned satisfies the
+    linear equations to rounding).  The
+    gradient of a solve (``batch_vjp``) is exact only at such a point.
+
+    The problem data are ``batch_solve``'s (P optional; ONE P, A, G and sing
+    byte with shared_matrices).  numpy inputs go through host staging, the
+    iterate is copied and the call synchronises; torch CUDA tensors are used in
+    place -- x, y, z, s are overwritten -- stream-ordered on torch's current
+    stream.  explicit_inverse is refused (SOCP_E_UNSUPPORTED).
+    Returns dict(x, y, z, s, status[, res]): status 0, or what stopped the
+    problem at its last good iterate (a KKT status, or DOMAIN_ERROR when no
+    step length is found); res holds, per problem, |rd|, |rp|, z's and the
+    off-centre measure |lam o lam - mu e| / mu at the returned point."""
+    L = _lib.load()
+    kind, offs, dim = cone_arrays(cones)
+    B = _size(x) // n
+    if B * n != _size(x):
+        raise ValueError(f"x: {_size(x)} elements is not a multiple of n={n}")
+    MB = 1 if shared_matrices else B
+    _check_sizes(B, c=(c, B * n), A=(A if m else None, MB * m * n), b=(b if m else None, B * m), G=(G, MB * k * n),
+                 h=(h, B * k), sing=(sing, MB), P=(P, MB * n * n), y=(y if m else None, B * m), z=(z, B * k),
+                 s=(s, B * k))
+    P = _check_P(P, G, MB, n)
+    dev = _is_torch(G)
+    f64 = "torch.float64"
+    _same_side(dev, G, c=(c, f64), A=(A if m else None, f64), b=(b if m else None, f64), h=(h, f64),
+               sing=(sing, "torch.uint8"), x=(x, f64), y=(y if m else None, f64), z=(z, f64), s=(s, f64))
+    ctx = ctx or default_context()
+    if dev:
+        import torch
+        ctx.bind_torch_stream()
+        out = dict(x=x, y=y, z=z, s=s, status=torch.empty(B, dtype=torch.int32, device=G.device))
+        if res:
+            out["res"] = torch.empty(4 * B, dtype=torch.float64, device=G.device)
+        ins = dict(c=c, A=A, b=b, G=G, h=h, sing=sing)
+    else:
+        out = dict(x=np.array(x, np.float64).reshape(-1), y=np.array(y if m else [], np.float64).reshape(-1),
+                   z=np.array(z, np.float64).reshape(-1), s=np.array(s, np.float64).reshape(-1),
+                   status=np.zeros(B, np.int32))
+        if res:
+            out["res"] = np.zeros(4 * B)
+        ins = dict(c=_host(c), A=_host(A), b=_host(b), G=_host(G), h=_host(h),
+                   sing=None if sing is None else _host(sing, np.uint8))
+    p = _lib.ptr
+    _lib.check(L.socp_batch_centre(
+        ctx.handle, _lib.Dims(B, n, m, k, len(kind)), p(kind), p(offs), p(dim), p(P), p(ins["c"]),
+        p(ins["A"] if m else None), p(ins["b"] if m else None), p(ins["G"]), p(ins["h"]), p(ins["sing"]), int(steps),
+        _vjp_flags(dev, force_large, shared_matrices, explicit_inverse), p(out["x"]), p(out["y"] if m else None),
+        p(out["z"]), p(out["s"]), p(out["status"]), p(out.get("res"))))
+    return out
+
+
+VJP_OUTPUTS = ("dc", "db", "dh", "dP", "dA", "dG", "ux", "uy", "uz")
+
+
+def batch_vjp(cones, n, m, k, A, G, sing, x, y, z, s, gx=None, gy=None, gz=None, gs=None, *, P=None, skip=None,
+              want=None, out=None, centre_steps=0, c=None, b=None, h=None, ctx=None, force_large=False,
+              shared_matrices=False, explicit_inverse=False):
+    """The gradient of a solve at the point (x, y, z, s) (socp_batch_vjp): given
+    the upstream gradients gx, gy, gz, gs = dL/d(x, y, z, s) (None: zero), solve
+    the block system of ``batch_kkt_solve`` at (s, z) for the right-hand side
+    (gx - G'gs, gy, gz, 0), call the solution (ux, uy, uz, .), set
+    w = uz + gs, and return
+
+        dc = -ux    db = uy    dh = w
+        dP = -(ux x' + x ux')/2    dA = -(y ux' + uy x')    dG = -(z ux' + w x')
+
+    in the library's layout (column-major matrices, stacked batch-major).  This
+    is the derivative of the solution map at a point of the central path; a
+    solver's returned iterate is not one, so centre it first -- ``batch_centre``,
+    or centre_steps > 0 here, which needs c, b, h, centres a copy and returns
+    that point as x, y, z, s (a problem the centring stops is masked).
+    want: the outputs to compute, from VJP_OUTPUTS; None is all of them, without
+    dP, dA, dG when shared_matrices (those are sums over the batch, which the
+    library does not form: SOCP_E_UNSUPPORTED).  skip: int32 per problem;
+    a problem with skip != 0, or whose KKT solve fails, gets zeros in every
+    output and that value in status.  On `sing` problems gy must be zero.
+    out: a dict of the caller's own arrays for outputs of `want` (exact size, on
+    G's side); the others are allocated.
+    numpy arrays go through host staging; torch CUDA tensors are used in place,
+    stream-ordered.  Returns a dict of the outputs asked for plus status."""
+    L = _lib.load()
+    kind, offs, dim = cone_arrays(cones)
+    B = _size(x) // n
+    if B * n != _size(x):
+        raise ValueError(f"x: {_size(x)} elements is not a multiple of n={n}")
+    MB = 1 if shared_matrices else B
+    if want is None:
+        want = [w for w in VJP_OUTPUTS if not (shared_matrices and w in ("dP", "dA", "dG"))]
+    for w in want:
+        if w not in VJP_OUTPUTS:
+            raise ValueError(f"want: unknown output {w!r}")
+    _check_sizes(B, A=(A if m else None, MB * m * n), G=(G, MB * k * n), sing=(sing, MB), P=(P, MB * n * n),
+                 y=(y if m else None, B * m), z=(z, B * k), s=(s, B * k), gx=(gx, B * n),
+                 gy=(gy if m else None, B * m), gz=(gz, B * k), gs=(gs, B * k), skip=(skip, B))
+    P = _check_P(P, G, MB, n)
+    dev = _is_torch(G)
+    f64 = "torch.float64"
+    _same_side(dev, G, A=(A if m else None, f64), sing=(sing, "torch.uint8"), x=(x, f64), y=(y if m else None, f64),
+               z=(z, f64), s=(s, f64), gx=(gx, f64), gy=(gy if m else None, f64), gz=(gz, f64), gs=(gs, f64),
+               skip=(skip, "torch.int32"))
+    if centre_steps and (c is None or h is None or (m and b is None)):
+        raise ValueError("centre_steps > 0 needs c, b and h")
+    ctx = ctx or default_context()
+    given, out = out, {}
+    if centre_steps:
+        pt = [None if v is None else (v.clone() if dev else v) for v in (x, y if m else None, z, s)]
+        cen = batch_centre(cones, n, m, k, c, A, b, G, h, sing, *pt, steps=centre_steps, P=P, ctx=ctx,
+                           force_large=force_large, shared_matrices=shared_matrices)
+        x, y, z, s = cen["x"], cen["y"], cen["z"], cen["s"]
+        out.update(x=x, y=y, z=z, s=s)
+        if skip is None:
+            skip = cen["status"]
+        elif dev:
+            import torch
+            skip = torch.where(skip != 0, skip, cen["status"])
+        else:
+            skip = np.where(np.asarray(skip) != 0, skip, cen["status"]).astype(np.int32)
+    sizes = dict(dc=B * n, db=B * m, dh=B * k, dP=B * n * n, dA=B * m * n, dG=B * k * n, ux=B * n, uy=B * m,
+                 uz=B * k)
+    if dev:
+        import torch
+        ctx.bind_torch_stream()
+        new = lambda cnt, dt=torch.float64: torch.empty(cnt, dtype=dt, device=G.device)  # noqa: E731
+        status = new(B, torch.int32)
+        arg = lambda v, dt=None: v  # noqa: E731
+    else:
+        new = lambda cnt: np.zeros(cnt)  # noqa: E731
+        status = np.zeros(B, np.int32)
+        arg = lambda v, dt=np.float64: None if v is None else _host(v, dt)  # noqa: E731
+    for w in want:
+        mine = None if given is None else given.get(w)
+        if mine is not None:
+            _check_sizes(B, **{w: (mine, sizes[w])})
+            _same_side(dev, G, **{w: (mine, f64)})
+            if not dev and not (isinstance(mine, np.ndarray) and mine.dtype == np.float64
+                                and mine.flags.c_contiguous):
+                raise ValueError(f"out[{w!r}] must be a contiguous float64 array")
+        out[w] = new(sizes[w]) if mine is None else mine
+    out["status"] = status
+    p = _lib.ptr
+
+    def po(key):  # NULL for an output not asked for, or empty (m = 0)
+        v = out.get(key)
+        return p(v) if v is not None and key in want and _size(v) else None
+    ins = [arg(v) for v in (A if m else None, G)] + [arg(sing, np.uint8)] + [
+        arg(v) for v in (x, y if m else None, z, s, gx, gy if m else None, gz, gs)] + [arg(skip, np.int32)]
+    _lib.check(L.socp_batch_vjp(
+        ctx.handle, _lib.Dims(B, n, m, k, len(kind)), p(kind), p(offs), p(dim), p(P), *[p(v) for v in ins],
+        _vjp_flags(dev, force_large, shared_matrices, explicit_inverse),
+        *[po(key) for key in VJP_OUTPUTS], p(status)))
+    return out
 
 
 class DenseHandle:
