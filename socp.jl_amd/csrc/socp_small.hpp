@@ -4041,6 +4041,194 @@ struct Small {
 #endif
   }
 
+  // The exact-fit kernel's driver: solve_socp (solver.jl:40-153) as one loop,
+  // a trip per factorisation.  A trip is the probe of G'G (XK_PROBE, only when
+  // the call gives no `sing`), the initial point (XK_INIT, unless warm-started)
+  // or an iteration (XK_ITER); what differs between them is steered by `kind`,
+  // so factor() and the solve body are inlined once, as in run().  The
+  // operations and their order are run<0>'s for MODE_SOLVE: the same bits.
+  // The trip kind is the only state a trip hands to the next; `fac` kinds are
+  // named per request and h_formed is a value of the call, as in run().
+  enum : int { XK_PROBE, XK_INIT, XK_ITER };
+  template <bool OV>
+  __device__ __forceinline__ void run_exact(int64_t p, bool h_formed) {
+    static_assert(EX && OV && !QP && !XI, "the exact-fit solver kernel");
+    STAMP(SP_LOAD);
+    dbg_p = p;
+    int status = ST_MAXIT, iters = 0, it = 0;
+    double nd = NAN, np_ = NAN, gap = NAN;
+    double ll = 0.0;
+    bool dm_aa = false;
+    int first = XK_INIT;
+    if (a.flags & F_WARM) {
+      for (int j = lane; j < n; j += 64) LDS(X_ + j) = a.x[p * n + j];
+      for (int i = lane; i < m; i += 64) LDS(Y_ + i) = a.y[p * m + i];
+      for (int i = lane; i < k; i += 64) {
+        LDS(Z_ + i) = a.z[p * k + i];
+        LDS(S_ + i) = a.s[p * k + i];
+      }
+      first = XK_ITER;
+    }
+    SYNC();
+    int kind = first;
+    if (a.sing) {
+      sing = uni((int)a.sing[(a.flags & F_SHARED) ? 0 : p]) != 0;
+    } else {
+      sing = false;
+      kind = XK_PROBE;
+    }
+    for (;;) {
+      LANE_IDS();
+      int fac;
+      bool aa;
+      if (kind == XK_ITER) {  // residuals (solver.jl:109-118), compute_scaling (:106), exit test (:122)
+        MARK_BEGIN("exact pre ITER");
+        STAMP(SP_OTHER);
+        // (the exits and their order: case MP_ITER of run())
+        if (it >= a.maxit && !a.res) break;
+        const bool dm = resid_scaling<!(SOCP_KO & 2), !(SOCP_KO & 4096)>(nd, np_, gap, ll, dm_aa);
+        STAMP(SP_RESID);
+        if (it >= a.maxit) break;
+        STAMP(SP_VOP);
+        if (dm) {
+          status = ST_DOMAIN;
+          break;
+        }
+        if (nd + np_ + gap < a.tol) {
+          status = ST_CONVERGED;
+          break;
+        }
+        // (resid_scaling's G x pass has left this scaling's U in LDS)
+        fac = (!(SOCP_KO & (2 | 4 | 16 | 4096)) && fuse_u()) ? FAC_SCALED_U : FAC_SCALED;
+        aa = sing;
+      } else {
+        MARK_BEGIN("exact pre IDENT");
+        scaling_identity();
+        // (FAC_IDENT_H on a problem's first factorisation only: a probe factors the tiles in place)
+        if (kind == XK_INIT) {  // initial point: the KKT system with W = I (solver.jl:68-84)
+          for (int j = lane; j < n; j += 64) LDS(RD + j) = -LDS(C_ + j);
+          for (int i = lane; i < m; i += 64) LDS(RP + i) = LDS(B_ + i);
+          for (int i = lane; i < k; i += 64) {
+            LDS(DZ + i) = LDS(H_ + i);
+            LDS(DS + i) = 0.0;
+          }
+          SYNC();
+          fac = (h_formed && a.sing) ? FAC_IDENT_H : FAC_IDENT;
+          aa = sing;
+        } else {  // Problem's `sing` (Socp.jl:49-56): is G'G positive definite?
+          fac = h_formed ? FAC_IDENT_H : FAC_IDENT;
+          aa = false;
+        }
+      }
+      MARK_BEGIN("exact factor");
+      const int fst = factor<OV>(fac, aa);
+      MARK_BEGIN("exact post factor");
+      if (kind == XK_PROBE) {
+        sing = (fst == ST_CHOL_H);
+        kind = uni(first);
+        continue;
+      }
+      if (fst) {
+        status = fst;
+        break;
+      }
+      // the solves (densesolver.jl:54-90): the initial point's one, or the
+      // affine and the combined one of an iteration
+      int ret = kind == XK_INIT ? RET_INIT : RET_AFFINE;
+      bool stop = false;
+      for (;;) {
+        MARK_BEGIN("case MP_SOLVE_HEAD");
+        STAMP(SP_OTHER);
+        solve_head();
+        STAMP(SP_VOP);
+        MARK_BEGIN("case MP_SOLVE_MAT");
+        solve_matrix_part(ret == RET_INIT);
+        STAMP(SP_SOLVE);
+        MARK_BEGIN("case MP_SOLVE_TAIL");
+        int dom = 0;
+        const double tstep = solve_tail(ret != RET_INIT, dm_aa, dom);
+        STAMP(SP_VOP);
+        if (ret == RET_INIT) {  // cone shift (solver.jl:86-104)
+          double alphp, alphd;  // max_step(-iz), max_step(iz)
+          maxstep_op(RZ, alphp, alphd);
+          for (int j = lane; j < n; j += 64) LDS(X_ + j) = LDS(RX + j);
+          for (int i = lane; i < m; i += 64) LDS(Y_ + i) = LDS(RY + i);
+          for (int i = lane; i < k; i += 64) {
+            const double iz = LDS(RZ + i), e = e_of(i);
+            LDS(S_ + i) = (fabs(alphp) < a.init_eps) ? -iz : -iz + (1.0 + alphp) * e;
+            LDS(Z_ + i) = (fabs(alphd) < a.init_eps) ? iz : iz + (1.0 + alphd) * e;
+          }
+          SYNC();
+          kind = XK_ITER;
+          break;
+        }
+        if (dom) {
+          status = ST_DOMAIN;
+          stop = true;
+          break;
+        }
+        if (ret == RET_AFFINE) {  // centering + corrector, then the combined solve
+          affine_post(tstep, ll);
+          STAMP(SP_STEP);
+          ret = RET_COMBINED;
+          continue;
+        }
+        // combined direction: step and update (solver.jl:143-150)
+        const double stp = tstep * a.step;
+        {  // every read first, then the updates (n = 64, m = 16, k = 96)
+          constexpr int NS = KP > 64 ? 2 : 1;
+          const int ly = lane < MPAD ? lane : 0;
+          const double xo = LDS(X_ + lane), rx = LDS(RX + lane), yo = LDS(Y_ + ly), ry = LDS(RY + ly);
+          double zo[NS], rz[NS], so[NS], rs[NS];
+#pragma unroll
+          for (int t = 0; t < NS; ++t) {
+            const int i = 64 * t + lane;
+            zo[t] = LDS(Z_ + i);
+            rz[t] = LDS(RZ + i);
+            so[t] = LDS(S_ + i);
+            rs[t] = LDS(RS + i);
+          }
+          if (lane < n) LDS(X_ + lane) = xo + rx * stp;
+          if (lane < m) LDS(Y_ + lane) = yo + ry * stp;
+#pragma unroll
+          for (int t = 0; t < NS; ++t) {
+            const int i = 64 * t + lane;
+            if (i < k) {
+              LDS(Z_ + i) = zo[t] + rz[t] * stp;
+              LDS(S_ + i) = so[t] + rs[t] * stp;
+            }
+          }
+        }
+        SYNC();
+        STAMP(SP_STEP);
+        iters = ++it;
+        break;
+      }
+      if (stop) break;
+    }
+    MARK_BEGIN("exact store");
+    for (int j = lane; j < n; j += 64) a.x[p * n + j] = LDS(X_ + j);
+    for (int i = lane; i < m; i += 64) a.y[p * m + i] = LDS(Y_ + i);
+    for (int i = lane; i < k; i += 64) {
+      a.z[p * k + i] = LDS(Z_ + i);
+      a.s[p * k + i] = LDS(S_ + i);
+    }
+    if (lane == 0) {
+      if (a.res) {
+        a.res[3 * p + 0] = nd;
+        a.res[3 * p + 1] = np_;
+        a.res[3 * p + 2] = gap;
+      }
+      a.iters[p] = iters;
+      a.status[p] = status;
+    }
+    SYNC();
+    STAMP(SP_STORE);
+#ifdef SOCP_DIAG
+    if (lane == 0) reinterpret_cast<unsigned long long*>(socp_lds + O_STAMPS)[NSTAMP] += iters;
+#endif
+  }
+
   __device__ __forceinline__ void flush_stamps() {
 #ifdef SOCP_DIAG
     SYNC();
@@ -4070,7 +4258,10 @@ __global__ void __launch_bounds__(64, !small_km(KM).plugin && !small_km(KM).xi ?
     if ((int64_t)p >= args.B) break;
     if constexpr (init_overlap_kernel(NQ, NP, MQ, KM) && !(SOCP_KO & 1)) {
       const bool h_formed = S.template load_problem<true>(p);
-      S.template run<0, false, true>(p, h_formed);
+      if constexpr (K.exact)
+        S.template run_exact<true>(p, h_formed);
+      else
+        S.template run<0, false, true>(p, h_formed);
     } else {
       S.load_problem(p);
       S.template run<K.plugin, K.di>(p);
