@@ -415,7 +415,8 @@ int socp_batch_centre(socp_ctx* ctx, const socp_dims* dims,
  * the block system's solve when dy != 0.
  * flags: SOCP_F_DEVICE_PTRS | SOCP_F_FORCE_LARGE; SOCP_F_SHARED_MATRICES (one
  * P, A, G, sing) only while dP, dA and dG are NULL -- with one of them it
- * returns SOCP_E_UNSUPPORTED (those are sums over the batch, not formed here);
+ * returns SOCP_E_UNSUPPORTED (those are sums over the batch, which
+ * socp_batch_vjp_sum below forms);
  * SOCP_F_EXPLICIT_INVERSE returns SOCP_E_UNSUPPORTED, every other bit
  * SOCP_E_INVALID. */
 int socp_batch_vjp(socp_ctx* ctx, const socp_dims* dims,
@@ -426,6 +427,39 @@ int socp_batch_vjp(socp_ctx* ctx, const socp_dims* dims,
                    const int32_t* skip, int32_t flags,
                    double* dc, double* db, double* dh, double* dP, double* dA, double* dG,
                    double* ux, double* uy, double* uz, int32_t* status);
+
+/* The adjoint of a shared-matrix batch with the gradients of its ONE P, A and
+ * G.  P, A, G are ONE matrix each and sing ONE byte or NULL, and
+ * SOCP_F_SHARED_MATRICES must be set (without it: SOCP_E_INVALID).  dc, db, dh,
+ * ux, uy, uz and status are per problem and bitwise those of socp_batch_vjp
+ * with SOCP_F_SHARED_MATRICES on the same inputs (the same kernels, launched
+ * the same way).  dP[n^2], dA[m n], dG[k n], column-major, are the sums of the
+ * per-problem outer products over the problems that count, on(p) meaning
+ * status[p] == 0, with w_p = fl(uz_p + gs_p) (the bits of dh_p):
+ *     dG = -sum_{on(p)} (z_p ux_p' + w_p x_p')
+ *     dA = -sum_{on(p)} (y_p ux_p' + uy_p x_p')
+ *     dP = -(M + M')/2,   M = sum_{on(p)} ux_p x_p'
+ * A problem with skip[p] != 0 or a failed KKT solve contributes nothing (its
+ * terms are selected away, not multiplied by zero: the sums stay finite).  dP
+ * is symmetric in bits.  Each of dP, dA, dG may be NULL and is then skipped;
+ * dA is skipped when m = 0; with all three NULL the call is socp_batch_vjp's.
+ * The sums are deterministic: the same bits from run to run, with host or
+ * device pointers, and whichever other outputs are asked for.  The batch is
+ * cut into slabs of consecutive problems by a rule that depends on (batch, n,
+ * m, k) alone (socp_debug_vjp_sum_plan); one launch writes each
+ * slab's partial sums, a second adds them in ascending slab order.  No atomics.
+ * flags: SOCP_F_SHARED_MATRICES, with SOCP_F_DEVICE_PTRS (stream-ordered, no
+ * synchronisation) and SOCP_F_FORCE_LARGE allowed; SOCP_F_EXPLICIT_INVERSE
+ * returns SOCP_E_UNSUPPORTED, every other bit SOCP_E_INVALID. */
+int socp_batch_vjp_sum(socp_ctx* ctx, const socp_dims* dims,
+                       const int32_t* cone_kind, const int32_t* cone_offs, const int32_t* cone_dim,
+                       const double* P, const double* A, const double* G, const uint8_t* sing,
+                       const double* x, const double* y, const double* z, const double* s,
+                       const double* gx, const double* gy, const double* gz, const double* gs,
+                       const int32_t* skip, int32_t flags,
+                       double* dc, double* db, double* dh, /* per problem, as socp_batch_vjp */
+                       double* dP, double* dA, double* dG, /* ONE n x n, m x n, k x n */
+                       double* ux, double* uy, double* uz, int32_t* status);
 
 /* The same two methods split the way the reference's KKTSolver plugin is
  * (densesolver.jl): a handle stands for a batch of DenseSolver objects.
@@ -759,6 +793,13 @@ int socp_debug_slot_plan(const socp_dims* dims, const int32_t* kind, const int32
  * the results are the same bits. */
 int socp_debug_exact_fit(const socp_dims* dims, const int32_t* kind, const int32_t* offs,
                          const int32_t* dim, int32_t flags, int32_t* exact);
+
+/* Testing hook (host only, no device work): how socp_batch_vjp_sum cuts a batch
+ * of dims->batch >= 1 problems of this n, m, k (ncones is not read): *slabs runs
+ * of *slab_problems consecutive problems, the last one ragged.  slab_problems
+ * is 512, doubled while there is more than one slab and the partial sums,
+ * slabs * (k n + m n + n^2) doubles, would pass 64 MiB. */
+int socp_debug_vjp_sum_plan(const socp_dims* dims, int64_t* slabs, int64_t* slab_problems);
 
 #ifdef __cplusplus
 }

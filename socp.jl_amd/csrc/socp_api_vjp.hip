@@ -1,10 +1,10 @@
 // socp_api_vjp.hip — differentiable solves (include/socp.h):
-// socp_batch_centre and socp_batch_vjp.  Host code only; the kernels are
+// socp_batch_centre, socp_batch_vjp and socp_batch_vjp_sum.  Host code only; the kernels are
 // socp_vjp.hip's, and every KKT solve is the fused plugin entry itself
 // (socp_batch_kkt_solve_qp on device buffers: choose_engine and the kernels of
 // a caller's own call), so no solver or plugin kernel is launched differently.
 // That entry uses the context's B_C, B_CNT and B_LWS buffers; what is staged
-// here stays clear of them.
+// here stays clear of them.  socp_batch_vjp_sum's partial sums live in B_VSUM.
 #include "socp_host.hpp"
 #include "socp_vjp.hpp"
 
@@ -142,19 +142,16 @@ extern "C" int socp_batch_centre(socp_ctx* ctx, const socp_dims* dims, const int
   return 0;
 }
 
-extern "C" int socp_batch_vjp(socp_ctx* ctx, const socp_dims* dims, const int32_t* cone_kind,
-                              const int32_t* cone_offs, const int32_t* cone_dim, const double* Pm, const double* A,
-                              const double* G, const uint8_t* sing, const double* x, const double* y,
-                              const double* z, const double* s, const double* gx, const double* gy,
-                              const double* gz, const double* gs, const int32_t* skip, int32_t flags, double* dc,
-                              double* db, double* dh, double* dP, double* dA, double* dG, double* ux, double* uy,
-                              double* uz, int32_t* status) {
-  if (!ctx) return fail(SOCP_E_INVALID, "ctx is NULL");
-  TRY(check_flags(flags, "socp_batch_vjp"));
-  if ((flags & SOCP_F_SHARED_MATRICES) && (dP || dA || dG))
-    return fail(SOCP_E_UNSUPPORTED,
-                "socp_batch_vjp: dP, dA and dG with SOCP_F_SHARED_MATRICES are sums over the batch, which this "
-                "entry does not form");
+namespace {
+
+// Both adjoint entries after their flag checks.  `sum`: dP, dA and dG are ONE matrix each, the
+// sums over the batch (socp_batch_vjp_sum); the per-problem path is launched as without it.
+int vjp_run(socp_ctx* ctx, const socp_dims* dims, const int32_t* cone_kind, const int32_t* cone_offs,
+            const int32_t* cone_dim, const double* Pm, const double* A, const double* G, const uint8_t* sing,
+            const double* x, const double* y, const double* z, const double* s, const double* gx, const double* gy,
+            const double* gz, const double* gs, const int32_t* skip, int32_t flags, double* dc, double* db,
+            double* dh, double* dP, double* dA, double* dG, double* ux, double* uy, double* uz, int32_t* status,
+            bool sum) {
   ConeTable cones;
   memset(&cones, 0, sizeof(cones));
   int degree = 0;
@@ -193,9 +190,17 @@ extern "C" int socp_batch_vjp(socp_ctx* ctx, const socp_dims* dims, const int32_
   TRY(st.in(X::B_RES, gs, Bk, &a.gs));
   TRY(st.in(X::B_IT, skip, (size_t)B, &a.skip));
   TRY(st.out(X::B_ST, status, (size_t)B, false, &a.status));
-  TRY(st.out(X::B_EP, dP, (size_t)B * n * n, false, &a.dP));
-  TRY(st.out(X::B_EA, m > 0 ? dA : nullptr, (size_t)B * m * n, false, &a.dA));
-  TRY(st.out(X::B_EG, dG, (size_t)B * k * n, false, &a.dG));
+  // dP, dA, dG: per problem, written by vjp_assemble; or the batch's one, written by vjp_sum_combine
+  const size_t GB = sum ? 1 : (size_t)B;
+  double *dPd = nullptr, *dAd = nullptr, *dGd = nullptr;
+  TRY(st.out(X::B_EP, dP, GB * n * n, false, &dPd));
+  TRY(st.out(X::B_EA, m > 0 ? dA : nullptr, GB * m * n, false, &dAd));
+  TRY(st.out(X::B_EG, dG, GB * k * n, false, &dGd));
+  if (!sum) {
+    a.dP = dPd;
+    a.dA = dAd;
+    a.dG = dGd;
+  }
   // the six vector outputs: with host pointers, one run of the staging buffer each
   double* const vuser[6] = {dc, m > 0 ? db : nullptr, dh, ux, m > 0 ? uy : nullptr, uz};
   const size_t vcnt[6] = {Bn, Bm, Bk, Bn, Bm, Bk};
@@ -242,11 +247,79 @@ extern "C" int socp_batch_vjp(socp_ctx* ctx, const socp_dims* dims, const int32_
   a.uz = u[2];
   a.kst = kst;
   HIPCHK(vjp_assemble_launch(a, B, ctx->stream));
+  if (sum && (dPd || dAd || dGd)) {
+    // the partials' size and the slab rule depend on (B, n, m, k) alone, not on which sums are asked for
+    VjpSumArgs q;
+    memset(&q, 0, sizeof(q));
+    q.x = a.x;
+    q.y = a.y;
+    q.z = a.z;
+    q.ux = u[0];
+    q.uy = u[1];
+    q.uz = u[2];
+    q.gs = a.gs;
+    q.status = a.status;
+    q.dP = dPd;
+    q.dA = dAd;
+    q.dG = dGd;
+    q.B = B;
+    q.n = n;
+    q.m = m;
+    q.k = k;
+    vjp_sum_plan(B, n, m, k, &q.slabs, &q.slab);
+    TRY(st.reserve(X::B_VSUM, (size_t)q.slabs * ((size_t)k + m + n) * n * sizeof(double)));
+    q.part = (double*)ctx->buf[X::B_VSUM].p;
+    HIPCHK(vjp_sum_partial_launch(q, ctx->stream));
+    HIPCHK(vjp_sum_combine_launch(q, ctx->stream));
+  }
   for (int i = 0; i < 6; ++i) TRY(st.back(vuser[i], vdev[i], vcnt[i]));
-  TRY(st.back(dP, a.dP, (size_t)B * n * n));
-  TRY(st.back(m > 0 ? dA : nullptr, a.dA, (size_t)B * m * n));
-  TRY(st.back(dG, a.dG, (size_t)B * k * n));
+  TRY(st.back(dP, dPd, GB * n * n));
+  TRY(st.back(m > 0 ? dA : nullptr, dAd, GB * m * n));
+  TRY(st.back(dG, dGd, GB * k * n));
   TRY(st.back(status, a.status, (size_t)B));
   if (!dev) HIPCHK(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int socp_batch_vjp(socp_ctx* ctx, const socp_dims* dims, const int32_t* cone_kind,
+                              const int32_t* cone_offs, const int32_t* cone_dim, const double* Pm, const double* A,
+                              const double* G, const uint8_t* sing, const double* x, const double* y,
+                              const double* z, const double* s, const double* gx, const double* gy,
+                              const double* gz, const double* gs, const int32_t* skip, int32_t flags, double* dc,
+                              double* db, double* dh, double* dP, double* dA, double* dG, double* ux, double* uy,
+                              double* uz, int32_t* status) {
+  if (!ctx) return fail(SOCP_E_INVALID, "ctx is NULL");
+  TRY(check_flags(flags, "socp_batch_vjp"));
+  if ((flags & SOCP_F_SHARED_MATRICES) && (dP || dA || dG))
+    return fail(SOCP_E_UNSUPPORTED,
+                "socp_batch_vjp: dP, dA and dG with SOCP_F_SHARED_MATRICES are sums over the batch, which this "
+                "entry does not form (socp_batch_vjp_sum does)");
+  return vjp_run(ctx, dims, cone_kind, cone_offs, cone_dim, Pm, A, G, sing, x, y, z, s, gx, gy, gz, gs, skip, flags,
+                 dc, db, dh, dP, dA, dG, ux, uy, uz, status, false);
+}
+
+extern "C" int socp_batch_vjp_sum(socp_ctx* ctx, const socp_dims* dims, const int32_t* cone_kind,
+                                  const int32_t* cone_offs, const int32_t* cone_dim, const double* Pm,
+                                  const double* A, const double* G, const uint8_t* sing, const double* x,
+                                  const double* y, const double* z, const double* s, const double* gx,
+                                  const double* gy, const double* gz, const double* gs, const int32_t* skip,
+                                  int32_t flags, double* dc, double* db, double* dh, double* dP, double* dA,
+                                  double* dG, double* ux, double* uy, double* uz, int32_t* status) {
+  if (!ctx) return fail(SOCP_E_INVALID, "ctx is NULL");
+  TRY(check_flags(flags, "socp_batch_vjp_sum"));
+  if (!(flags & SOCP_F_SHARED_MATRICES))
+    return fail(SOCP_E_INVALID, "socp_batch_vjp_sum: SOCP_F_SHARED_MATRICES must be set (dP, dA and dG are the "
+                                "gradients of the batch's one P, A and G)");
+  return vjp_run(ctx, dims, cone_kind, cone_offs, cone_dim, Pm, A, G, sing, x, y, z, s, gx, gy, gz, gs, skip, flags,
+                 dc, db, dh, dP, dA, dG, ux, uy, uz, status, true);
+}
+
+extern "C" int socp_debug_vjp_sum_plan(const socp_dims* dims, int64_t* slabs, int64_t* slab_problems) {
+  if (!dims || !slabs || !slab_problems) return fail(SOCP_E_INVALID, "socp_debug_vjp_sum_plan: NULL pointer");
+  if (dims->batch < 1 || dims->batch > kMaxBatch || dims->n < 1 || dims->m < 0 || dims->k < 1)
+    return fail(SOCP_E_INVALID, "socp_debug_vjp_sum_plan: batch, n and k must be at least 1 and m at least 0");
+  vjp_sum_plan(dims->batch, dims->n, dims->m, dims->k, slabs, slab_problems);
   return 0;
 }

@@ -72,10 +72,10 @@ struct socp_ctx {
   // B_EX: the equilibration exponents; B_E*: the scaled copies of device-pointer inputs, and with
   // host pointers the staging of socp_batch_equilibrate's D, E, F
   // B_VST: the fused KKT solve's status inside socp_batch_centre / socp_batch_vjp; B_VOUT: the staging of
-  // socp_batch_vjp's vector outputs
+  // socp_batch_vjp's vector outputs; B_VSUM: socp_batch_vjp_sum's per-slab partial sums
   enum { B_C, B_A, B_B, B_G, B_H, B_SING, B_X, B_Y, B_Z, B_S, B_IT, B_ST, B_RES, B_DX, B_DY,
          B_DZ, B_DS, B_CX, B_CY, B_CZ, B_CS, B_CNT, B_LWS, B_ERR, B_P, B_EX, B_EC, B_EA, B_EB,
-         B_EG, B_EH, B_EP, B_VST, B_VOUT, NB };
+         B_EG, B_EH, B_EP, B_VST, B_VOUT, B_VSUM, NB };
   socp::host::DevBuf buf[NB];
 };
 

@@ -5,6 +5,8 @@
 // between centre_rhs and centre_update, and between vjp_rhs and vjp_assemble,
 // is the fused plugin entry's own launch (socp_api_vjp.hip); the last centring
 // pass refines its step by a second one (centre_refine, centre_add).
+// socp_batch_vjp_sum's two kernels (vjp_sum_partial, vjp_sum_combine) are at the
+// end: the batch is their inner dimension, not their grid.
 //
 // Matrices are column-major: a column's dot product with a vector (G'z, A'y,
 // Px with P symmetric, G'gs) is one column per wavefront, lanes down the column,
@@ -391,7 +393,151 @@ __global__ __launch_bounds__(NT) void vjp_assemble_kernel(const VjpArgs a) {
   }
 }
 
+// ------------------------------------------------------- socp_batch_vjp_sum
+// The sums over the batch (socp_vjp.hpp).  The three outputs are one stack of
+// 16-row tiles: dG's ceil(k/16), dA's ceil(m/16), M's ceil(n/16), by ceil(n/16)
+// column tiles.  A wavefront owns one 16 x 16 tile of one slab and walks the
+// slab four problems per v_mfma_f64_16x16x4_f64: the batch is the inner
+// dimension, so lane (r = lane & 15, q = lane >> 4) holds row i0 + r of problem
+// p0 + q's column vector as the A operand and column j0 + r of its row vector as
+// the B operand -- one 128-byte run per problem and tile edge.  A tile of dG is
+// two chains, (z, ux) and (w, x); of dA, (y, ux) and (uy, x); of M, (ux, x).
+// The four wavefronts of a workgroup are CW column tiles by 4 / CW row tiles
+// (CW = 4, 2, 1 as n > 32, n > 16, else), so that a row tile's operands are
+// fetched from memory once per workgroup and the other wavefronts hit the cache.
+// Rows, columns and problems out of range, and problems that do not count, are
+// 0.0 by selection: a failed solve's NaN is never an operand.
+constexpr int SUM_STEPS = 4;  // steps of four problems whose loads are in flight together
+
+struct SumTile {
+  const double *a0, *a1;  // the two chains' column vectors (a0 NULL: one chain); both chains' row vectors are ux, x
+  const double* a1b;      // added to a1's elements when not NULL (w = uz + gs)
+  int rows, lda;          // rows of the output, elements per problem of a0 / a1
+  int64_t off;            // the output's place in a slab's partials
+};
+
+__device__ inline bool sum_tile_of(const VjpSumArgs& a, int rt, SumTile* t) {
+  const int KT = (a.k + 15) >> 4, MT = (a.m + 15) >> 4;
+  t->a1b = nullptr;
+  if (rt < KT) {
+    if (!a.dG) return false;
+    *t = SumTile{a.z, a.uz, a.gs, a.k, a.k, 0};
+  } else if (rt < KT + MT) {
+    if (!a.dA) return false;
+    *t = SumTile{a.y, a.uy, nullptr, a.m, a.m, (int64_t)a.k * a.n};
+  } else {
+    if (!a.dP) return false;
+    *t = SumTile{nullptr, a.ux, nullptr, a.n, a.n, ((int64_t)a.k + a.m) * a.n};
+  }
+  return true;
+}
+
+__global__ __launch_bounds__(NT) void vjp_sum_partial_kernel(const VjpSumArgs a, int64_t items, int RG, int CG,
+                                                             int CW) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r = lane & 15, q = lane >> 4;
+  const int n = a.n, RW = NW / CW;
+  const int KT = (a.k + 15) >> 4, MT = (a.m + 15) >> 4, RT = KT + MT + ((n + 15) >> 4), CT = (n + 15) >> 4;
+  const int64_t out = ((int64_t)a.k + a.m + n) * n;
+  for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+    const int rg = (int)(item % RG), cg = (int)(item / RG % CG);
+    const int64_t slab = item / RG / CG;
+    const int rt = rg * RW + w / CW, ct = cg * CW + w % CW;
+    if (rt >= RT || ct >= CT) continue;
+    SumTile t;
+    if (!sum_tile_of(a, rt, &t)) continue;
+    const int i0 = (rt - (rt < KT ? 0 : rt < KT + MT ? KT : KT + MT)) << 4, j0 = ct << 4;
+    const bool rin = i0 + r < t.rows, cin = j0 + r < n;
+    const int64_t pbeg = slab * a.slab, pend = pbeg + a.slab < a.B ? pbeg + a.slab : a.B;
+    d4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+    // SUM_STEPS steps' operands are loaded before their matrix instructions issue: a step alone would wait
+    // one memory latency per four problems.  The accumulation order is the problems' order either way.
+    for (int64_t p0 = pbeg; p0 < pend; p0 += 4 * SUM_STEPS) {
+      double va0[SUM_STEPS], va1[SUM_STEPS], vux[SUM_STEPS], vx[SUM_STEPS];
+#pragma unroll
+      for (int u = 0; u < SUM_STEPS; ++u) {
+        // every load is from a valid address (a lane out of range reads its slab's first element) and does
+        // not wait for the status; what does not count is dropped by selection afterwards
+        const int64_t p = p0 + 4 * u + q;
+        const bool inb = p < pend;
+        const int64_t ps = inb ? p : pbeg;
+        const int st = a.status[ps];
+        const int64_t ea = ps * t.lda + (rin ? i0 + r : 0), eb = ps * n + (cin ? j0 + r : 0);
+        const double la0 = t.a0 ? t.a0[ea] : 0.0, la1 = t.a1[ea], lab = t.a1b ? t.a1b[ea] : 0.0;
+        const double lux = t.a0 ? a.ux[eb] : 0.0, lx = a.x[eb];
+        const bool on = inb && st == 0;
+        va0[u] = on && rin ? la0 : 0.0;
+        va1[u] = on && rin ? la1 + lab : 0.0;
+        vux[u] = on && cin ? lux : 0.0;
+        vx[u] = on && cin ? lx : 0.0;
+      }
+#pragma unroll
+      for (int u = 0; u < SUM_STEPS; ++u) {
+        if (t.a0) acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(va0[u], vux[u], acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(va1[u], vx[u], acc1, 0, 0, 0);
+      }
+    }
+    // C/D layout: lane (q, r) holds row q + 4 s, column r in register s
+    double* o = a.part + slab * out + t.off;
+    if (cin) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int i = i0 + q + 4 * s;
+        if (i < t.rows) o[(int64_t)(j0 + r) * t.rows + i] = t.a0 ? acc0[s] + acc1[s] : acc1[s];
+      }
+    }
+  }
+}
+
+// One thread per output element: the slabs' partials in ascending order, then the sign, and for dP
+// the mean of M's (i, j) and (j, i) sums -- the same expression for both, so dP is symmetric in bits.
+__global__ __launch_bounds__(NT) void vjp_sum_combine_kernel(const VjpSumArgs a) {
+  const int n = a.n;
+  const int64_t kn = (int64_t)a.k * n, mn = (int64_t)a.m * n, out = kn + mn + (int64_t)n * n;
+  for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < out; e += (int64_t)gridDim.x * NT) {
+    if (e < kn ? !a.dG : e < kn + mn ? !a.dA : !a.dP) continue;
+    const double* src = a.part + e;
+    double sum = 0.0;
+    if (e < kn + mn) {
+#pragma unroll 8
+      for (int64_t s = 0; s < a.slabs; ++s) sum += src[s * out];
+      if (e < kn)
+        a.dG[e] = 0.0 - sum;
+      else
+        a.dA[e - kn] = 0.0 - sum;
+    } else {
+      const int64_t f = e - kn - mn;
+      const int i = (int)(f % n), j = (int)(f / n);
+      const double* mir = a.part + kn + mn + (int64_t)i * n + j;
+      double tsum = 0.0;
+#pragma unroll 8
+      for (int64_t s = 0; s < a.slabs; ++s) {
+        sum += src[s * out];
+        tsum += mir[s * out];
+      }
+      a.dP[f] = 0.0 - (sum + tsum) * 0.5;
+    }
+  }
+}
+
 }  // namespace
+
+hipError_t vjp_sum_partial_launch(const VjpSumArgs& a, hipStream_t stream) {
+  const int CT = (a.n + 15) >> 4, RT = ((a.k + 15) >> 4) + ((a.m + 15) >> 4) + CT;
+  const int CW = CT >= 3 ? 4 : CT, RW = NW / CW;
+  const int RG = (RT + RW - 1) / RW, CG = (CT + CW - 1) / CW;
+  const int64_t items = a.slabs * RG * CG;
+  const int64_t grid = items < ((int64_t)1 << 20) ? items : (int64_t)1 << 20;  // (the kernel strides over the rest)
+  hipLaunchKernelGGL(vjp_sum_partial_kernel, dim3((unsigned)grid), dim3(NT), 0, stream, a, items, RG, CG, CW);
+  return hipGetLastError();
+}
+hipError_t vjp_sum_combine_launch(const VjpSumArgs& a, hipStream_t stream) {
+  const int64_t out = ((int64_t)a.k + a.m + a.n) * a.n;
+  const int64_t blocks = (out + NT - 1) / NT;
+  const int64_t grid = blocks < ((int64_t)1 << 20) ? blocks : (int64_t)1 << 20;
+  hipLaunchKernelGGL(vjp_sum_combine_kernel, dim3((unsigned)grid), dim3(NT), 0, stream, a);
+  return hipGetLastError();
+}
 
 hipError_t centre_rhs_launch(const CentreArgs& a, int64_t B, hipStream_t stream) {
   hipLaunchKernelGGL(centre_rhs_kernel, dim3((unsigned)B), dim3(NT), 0, stream, a);

@@ -1,6 +1,6 @@
 // socp_vjp.hpp — differentiable solves (include/socp.h socp_batch_centre,
-// socp_batch_vjp): the arguments and host launchers of the four
-// kernels in socp_vjp.hip.  Every pointer is a device pointer.
+// socp_batch_vjp, socp_batch_vjp_sum): the arguments and host
+// launchers of the kernels in socp_vjp.hip.  Every pointer is a device pointer.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -58,5 +58,38 @@ hipError_t centre_add_launch(const CentreArgs& a, const double* ex, const double
                              const double* es, int64_t B, hipStream_t stream);
 hipError_t vjp_rhs_launch(const VjpArgs& a, int64_t B, hipStream_t stream);
 hipError_t vjp_assemble_launch(const VjpArgs& a, int64_t B, hipStream_t stream);
+
+// socp_batch_vjp_sum: the gradients of a batch's one P, A and G as sums over the
+// problems with status 0,
+//   dG = -sum (z ux' + w x'), dA = -sum (y ux' + uy x'), dP = -(M + M')/2, M = sum ux x',
+// w = uz + gs.  The batch is cut into `slabs` runs of `slab` consecutive problems
+// (vjp_sum_plan); vjp_sum_partial writes one partial sum per slab and output into
+// `part`, slab s at part + s * (k n + m n + n^2): dG's k x n, dA's m x n, M's n x n,
+// column-major; vjp_sum_combine adds them in ascending slab order.
+constexpr int64_t VJP_SUM_SLAB = 512;               // problems per slab ...
+constexpr int64_t VJP_SUM_WS_CAP = (int64_t)64 << 20;  // ... doubled while the partials would pass this many bytes
+
+struct VjpSumArgs {
+  const double *x, *y, *z;     // the point (y NULL when m = 0)
+  const double *ux, *uy, *uz;  // the KKT solve's solution: NaN where it failed, never read there
+  const double* gs;            // NULL: zero
+  const int32_t* status;       // vjp_assemble's: a problem counts where it is 0
+  double* part;                // slabs * (k n + m n + n^2) doubles
+  double *dP, *dA, *dG;        // ONE n x n, m x n, k x n; each may be NULL and is then skipped
+  int64_t B, slab, slabs;
+  int32_t n, m, k;
+};
+
+// the slab rule, a pure function of (B, n, m, k); B >= 1
+inline void vjp_sum_plan(int64_t B, int n, int m, int k, int64_t* slabs, int64_t* slab) {
+  const int64_t out = ((int64_t)k + m + n) * n;
+  int64_t s = VJP_SUM_SLAB;
+  while ((B + s - 1) / s > 1 && (B + s - 1) / s * out * (int64_t)sizeof(double) > VJP_SUM_WS_CAP) s *= 2;
+  *slab = s;
+  *slabs = (B + s - 1) / s;
+}
+
+hipError_t vjp_sum_partial_launch(const VjpSumArgs& a, hipStream_t stream);
+hipError_t vjp_sum_combine_launch(const VjpSumArgs& a, hipStream_t stream);
 
 }  // namespace socp

@@ -108,6 +108,18 @@ def slot_plan(cones, k):
     return rot.value, k0.value, k1.value
 
 
+def vjp_sum_plan(B, n, m, k):
+    """(slabs, slab_problems) of socp_debug_vjp_sum_plan: how ``batch_vjp`` with
+    shared_matrices cuts a batch of B problems into runs of consecutive problems
+    when it sums dP, dA, dG -- a function of (B, n, m, k) alone.  Host only."""
+    d = _lib.Dims(int(B), int(n), int(m), int(k), 0)
+    slabs, slab = C.c_int64(), C.c_int64()
+    rc = _lib.load().socp_debug_vjp_sum_plan(C.byref(d), C.byref(slabs), C.byref(slab))
+    if rc:
+        raise SocpError(rc, _lib.load().socp_last_error().decode())
+    return slabs.value, slab.value
+
+
 def exact_fit(cones, n, m, k, *, flags=0):
     """socp_debug_exact_fit: whether a batch_solve of these dims, this cone
     table and these socp_params flags (``_lib.F_*``) runs the solver kernel
@@ -473,10 +485,15 @@ def batch_vjp(cones, n, m, k, A, G, sing, x, y, z, s, gx=None, gy=None, gz=None,
     or centre_steps > 0 here, which needs c, b, h, centres a copy and returns
     that point as x, y, z, s (a problem the centring stops is masked).
     want: the outputs to compute, from VJP_OUTPUTS; None is all of them, without
-    dP, dA, dG when shared_matrices (those are sums over the batch, which the
-    library does not form: SOCP_E_UNSUPPORTED).  skip: int32 per problem;
+    dP, dA, dG when shared_matrices.  skip: int32 per problem;
     a problem with skip != 0, or whose KKT solve fails, gets zeros in every
     output and that value in status.  On `sing` problems gy must be zero.
+    With shared_matrices, dP, dA and dG in `want` are the gradients of the
+    batch's ONE P, A and G (socp_batch_vjp_sum): ONE matrix each, of n*n, m*n
+    and k*n elements, the sum of the formulas above over the problems with
+    status 0 -- deterministic, the same bits on every run and with numpy or
+    torch inputs; dP is symmetric in bits.  The per-problem outputs are those
+    of the call without the three.
     out: a dict of the caller's own arrays for outputs of `want` (exact size, on
     G's side); the others are allocated.
     numpy arrays go through host staging; torch CUDA tensors are used in place,
@@ -503,6 +520,18 @@ def batch_vjp(cones, n, m, k, A, G, sing, x, y, z, s, gx=None, gy=None, gz=None,
                skip=(skip, "torch.int32"))
     if centre_steps and (c is None or h is None or (m and b is None)):
         raise ValueError("centre_steps > 0 needs c, b and h")
+    sizes = dict(dc=B * n, db=B * m, dh=B * k, dP=MB * n * n, dA=MB * m * n, dG=MB * k * n, ux=B * n, uy=B * m,
+                 uz=B * k)
+    # the gradients of shared matrices are sums over the batch: the entry that forms them
+    sums = shared_matrices and any(w in want for w in ("dP", "dA", "dG"))
+    for w in want:
+        mine = None if out is None else out.get(w)
+        if mine is not None:
+            _check_sizes(B, **{w: (mine, sizes[w])})
+            _same_side(dev, G, **{w: (mine, f64)})
+            if not dev and not (isinstance(mine, np.ndarray) and mine.dtype == np.float64
+                                and mine.flags.c_contiguous):
+                raise ValueError(f"out[{w!r}] must be a contiguous float64 array")
     ctx = ctx or default_context()
     given, out = out, {}
     if centre_steps:
@@ -518,8 +547,6 @@ def batch_vjp(cones, n, m, k, A, G, sing, x, y, z, s, gx=None, gy=None, gz=None,
             skip = torch.where(skip != 0, skip, cen["status"])
         else:
             skip = np.where(np.asarray(skip) != 0, skip, cen["status"]).astype(np.int32)
-    sizes = dict(dc=B * n, db=B * m, dh=B * k, dP=B * n * n, dA=B * m * n, dG=B * k * n, ux=B * n, uy=B * m,
-                 uz=B * k)
     if dev:
         import torch
         ctx.bind_torch_stream()
@@ -532,12 +559,6 @@ def batch_vjp(cones, n, m, k, A, G, sing, x, y, z, s, gx=None, gy=None, gz=None,
         arg = lambda v, dt=np.float64: None if v is None else _host(v, dt)  # noqa: E731
     for w in want:
         mine = None if given is None else given.get(w)
-        if mine is not None:
-            _check_sizes(B, **{w: (mine, sizes[w])})
-            _same_side(dev, G, **{w: (mine, f64)})
-            if not dev and not (isinstance(mine, np.ndarray) and mine.dtype == np.float64
-                                and mine.flags.c_contiguous):
-                raise ValueError(f"out[{w!r}] must be a contiguous float64 array")
         out[w] = new(sizes[w]) if mine is None else mine
     out["status"] = status
     p = _lib.ptr
@@ -547,7 +568,7 @@ def batch_vjp(cones, n, m, k, A, G, sing, x, y, z, s, gx=None, gy=None, gz=None,
         return p(v) if v is not None and key in want and _size(v) else None
     ins = [arg(v) for v in (A if m else None, G)] + [arg(sing, np.uint8)] + [
         arg(v) for v in (x, y if m else None, z, s, gx, gy if m else None, gz, gs)] + [arg(skip, np.int32)]
-    _lib.check(L.socp_batch_vjp(
+    _lib.check((L.socp_batch_vjp_sum if sums else L.socp_batch_vjp)(
         ctx.handle, _lib.Dims(B, n, m, k, len(kind)), p(kind), p(offs), p(dim), p(P), *[p(v) for v in ins],
         _vjp_flags(dev, force_large, shared_matrices, explicit_inverse),
         *[po(key) for key in VJP_OUTPUTS], p(status)))

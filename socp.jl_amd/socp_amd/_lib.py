@@ -43,6 +43,7 @@ EXPORTED = [
     "socp_batch_kkt_solve_qp", "socp_dense_create_qp",
     "socp_ingest_submit_qp", "socp_ingest_set_matrices_qp",
     "socp_batch_centre", "socp_batch_vjp",
+    "socp_batch_vjp_sum", "socp_debug_vjp_sum_plan",
 ]
 # declared and exported as well, but kept out of the list above: tests/test_abi.py compares that
 # list with the header's lower-case names
@@ -134,6 +135,9 @@ def load():
     if hasattr(L, "socp_batch_vjp"):  # differentiable solves (absent from older A/B builds)
         L.socp_batch_centre.argtypes = (common + [dp] * 6 + [u8p, C.c_int32, C.c_int32] + [dp] * 4 + [i32p, dp])
         L.socp_batch_vjp.argtypes = (common + [dp] * 3 + [u8p] + [dp] * 8 + [i32p, C.c_int32] + [dp] * 9 + [i32p])
+    if hasattr(L, "socp_batch_vjp_sum"):  # gradients of shared matrices (absent from older A/B builds)
+        L.socp_batch_vjp_sum.argtypes = L.socp_batch_vjp.argtypes
+        L.socp_debug_vjp_sum_plan.argtypes = [C.POINTER(Dims)] + [C.POINTER(C.c_int64)] * 2
     L.socp_generate.argtypes = common + [C.c_uint64, C.c_int64] + [dp] * 5
     L.socp_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.socp_kernel_times.argtypes = [vp, C.POINTER(C.c_float), C.c_int]

@@ -13,7 +13,10 @@ Tensors are flat, float64, contiguous CUDA tensors in the library's layout
 problem and stacked batch-major -- so a batch's G is, as a tensor, ``(B, n, k)``
 of columns: ``G.view(B, n, k)[p, j]`` is column j of problem p's k x n matrix
 (``M.transpose(1, 2).contiguous().view(-1)`` from a ``(B, k, n)`` tensor of
-matrices).  Gradients come back flat in the same layout.
+matrices).  Gradients come back flat in the same layout.  With shared matrices
+A, G and P are ONE matrix each, and so are their gradients: the sum over the
+batch of the per-problem gradients, formed on the device in a fixed order
+(``socp_batch_vjp_sum``), in the shape of the shared tensor.
 
 Everything is stream-ordered on torch's current stream; nothing synchronises.
 Importing this module needs torch but no GPU.
@@ -49,7 +52,8 @@ class SocpFunction(torch.autograd.Function):
     solve did not converge keeps the solver's iterate); status and iters are
     ``batch_solve``'s and carry no gradient.  A problem with a nonzero status,
     from the solve or from the centring, contributes exactly zero to every
-    gradient.  With shared matrices only c, b and h can require a gradient."""
+    gradient.  With shared matrices the gradients of A, G and P are sums over the
+    batch and come back in the shape of the one shared tensor."""
 
     @staticmethod
     def forward(ctx, cfg, c, A, b, G, h, P, sing):
@@ -86,14 +90,12 @@ class SocpFunction(torch.autograd.Function):
         if cfg.m == 0:
             need["A"] = need["b"] = False
         want = ["d" + key for key, on in need.items() if on]
-        if cfg.shared_matrices and any(w in want for w in ("dP", "dA", "dG")):
-            raise RuntimeError("SocpFunction: with shared matrices only c, b and h can require a gradient "
-                               "(dP, dA, dG would be sums over the batch, which socp_batch_vjp does not form)")
         cont = lambda g: None if g is None else g.contiguous().view(-1)  # noqa: E731
         r = S.batch_vjp(cfg.cones, cfg.n, cfg.m, cfg.k, A, G, sing, x, y if cfg.m else None, z, s, cont(gx),
                         cont(gy) if cfg.m else None, cont(gz), cont(gs), P=P, skip=skip, want=want, ctx=ctx.lib_ctx,
                         force_large=ctx.force_large, shared_matrices=cfg.shared_matrices)
-        return (None, r.get("dc"), r.get("dA"), r.get("db"), r.get("dG"), r.get("dh"), r.get("dP"), None)
+        like = lambda key, t: None if key not in r else r[key].view(t.shape)  # noqa: E731
+        return (None, r.get("dc"), like("dA", A), r.get("db"), like("dG", G), r.get("dh"), like("dP", P), None)
 
 
 class SocpLayer(torch.nn.Module):
@@ -102,9 +104,9 @@ class SocpLayer(torch.nn.Module):
     cones: ``batch_solve``'s cone table.  centre_steps: the Newton centring
     steps after the solve (0: differentiate at the solver's iterate, which is
     wrong by the iterate's distance from the central path).  shared_matrices:
-    one A, G (and P, sing) for the batch -- the parametric case, where c, b and
-    h are what is differentiated.  solve_options go to ``batch_solve`` (maxit,
-    tol, force_large, ctx, ...).
+    one A, G (and P, sing) for the batch -- the parametric case; c, b and h get
+    per-problem gradients, A, G and P the batch's sum.  solve_options go to
+    ``batch_solve`` (maxit, tol, force_large, ctx, ...).
 
     ``layer(c, A, b, G, h, P=None, sing=None)`` returns
     ``(x, y, z, s, status, iters)``; see ``SocpFunction`` and the module
