@@ -167,6 +167,58 @@ typedef struct socp_params {
  * so do socp_ingest_submit[_csc] and socp_sqr_solve_socp for the bit.
  * Without the flag nothing changes. */
 #define SOCP_F_EQUILIBRATE 1024
+/* Normalisation: the exit test ||rd|| + ||rp|| + z's < tol is absolute, so it
+ * depends on the units of c, b and h, which equilibration leaves alone.  With
+ * this flag c and (b, h) are first scaled by socp_batch_normalise's rule
+ * (below) -- two powers of two per problem, so scaling and unscaling are exact
+ * in fp64 -- then the problem is solved, then the iterates are unscaled.  The
+ * rule, per problem p:
+ *   nc = max_j |c_j|;
+ *   nb = max(max_i |b_i|, max_i |h_i|); the b term is absent when m = 0;
+ *   e(v) = -ilogb(v) for v finite and > 0, subnormals included, clamped to
+ *          [-256, 256];
+ *   e(v) = 0 for every other v: zero, Inf, and NaN anywhere in the vector;
+ *   ec = e(nc), eb = e(nb).  Afterwards the largest entry of c^, and of
+ *   (b^, h^), lies in [1, 2).
+ * The scaled problem:
+ *   c^ = ldexp(c, ec);
+ *   b^ = ldexp(b, eb), h^ = ldexp(h, eb);
+ *   P^ = ldexp(P, ec - eb);
+ *   A and G as given.
+ * The iterates, both ways:
+ *   forward: x^ = ldexp(x, eb), s^ = ldexp(s, eb), y^ = ldexp(y, ec),
+ *            z^ = ldexp(z, ec);
+ *   unscaling uses the negated exponents.
+ * The factors are per problem, with SOCP_F_SHARED_MATRICES too, since c, b and
+ * h stay per problem there.  One exception: with SOCP_F_SHARED_MATRICES and a
+ * P, nc and nb are the maxima over the whole batch, so that one P^ serves
+ * every problem (a maximum is exact in any order).
+ * Contract: every output (x, y, z, s, iters, status, res, the kernel name) is
+ * bitwise what this pipeline gives:
+ *   1. socp_batch_normalise on (P, c, b, h);
+ *   2. the same solve entry without the flag on the scaled data; with
+ *      SOCP_F_WARM_START the incoming iterate is scaled forward as above;
+ *   3. the unscaling of x, y, z, s.
+ * It follows that tol, init_eps and res[] refer to the NORMALISED problem:
+ * status == 0 implies 2^ec ||rd|| + 2^eb ||rp|| + 2^(ec+eb) z's < tol in the
+ * caller's units -- a test relative to the sizes of c and of (b, h).  The
+ * iterates are unscaled whatever the status.  The caller's inputs are never
+ * written: the scaled copies live in buffers of the context (with host
+ * pointers, the staged device copy is scaled in place); with device pointers
+ * the in/out iterate of a warm start is scaled in place and unscaled in place,
+ * also when the solver's launch returns an error.
+ * The SOCP_DUMP_DIR dump writes the caller's data.
+ * Honoured through params->flags by socp_batch_solve, socp_batch_solve_ex and
+ * socp_batch_solve_qp.  SOCP_F_DEVICE_PTRS, SOCP_F_WARM_START,
+ * SOCP_F_FORCE_LARGE, SOCP_F_EXPLICIT_INVERSE and SOCP_F_SHARED_MATRICES pass
+ * through.  With SOCP_F_EQUILIBRATE the order is equilibrate, normalise,
+ * solve, un-normalise, unscale; every step is exact, so both pipeline
+ * contracts hold together.  With SOCP_F_DETECT_INFEASIBLE the call returns
+ * SOCP_E_UNSUPPORTED (the rule's ratios change by 2^eb and 2^ec, so tau's
+ * meaning would move, as it does under equilibration); so do
+ * socp_ingest_submit[_csc] and socp_sqr_solve_socp for the bit.
+ * Without the flag nothing changes. */
+#define SOCP_F_NORMALISE 2048
 
 typedef struct socp_ctx socp_ctx;
 
@@ -308,6 +360,23 @@ int socp_batch_equilibrate(socp_ctx* ctx, const socp_dims* dims,
                            const double* G, const double* h, int32_t flags,
                            double* D, double* E, double* F,
                            double* Ps, double* cs, double* As, double* bs, double* Gs, double* hs);
+
+/* SOCP_F_NORMALISE's rule (above) on the device: the two exponents of every
+ * problem and the scaled data.  Outputs:
+ *   expo : 2 * batch int32, expo[2p] = ec and expo[2p+1] = eb of problem p --
+ *          always 2 * batch entries, all equal in the shared-P case;
+ *   Ps = ldexp(P, ec - eb) (the layout of P: ONE matrix with
+ *        SOCP_F_SHARED_MATRICES, which then takes the batch-wide pair);
+ *   cs = ldexp(c, ec), bs = ldexp(b, eb), hs = ldexp(h, eb), per problem.
+ * Every scaled value is exact, up to one rounding where a result is subnormal.
+ * P may be NULL, and b when m = 0.  Any output pointer may be NULL and is then
+ * skipped.  The inputs are not written.  flags: SOCP_F_DEVICE_PTRS
+ * (stream-ordered, no synchronisation) | SOCP_F_SHARED_MATRICES.  Only batch,
+ * n, m and k of dims are read (batch > 2^31-1 is rejected as everywhere). */
+int socp_batch_normalise(socp_ctx* ctx, const socp_dims* dims,
+                         const double* P, const double* c, const double* b, const double* h,
+                         int32_t flags, int32_t* expo,
+                         double* Ps, double* cs, double* bs, double* hs);
 
 /* Single-problem plugin entries.  They replace the two KKTSolver methods of
  * DenseSolver so the reference's own KKT golden (runtests.jl:95-128) runs

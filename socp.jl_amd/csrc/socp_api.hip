@@ -1,12 +1,13 @@
 // socp_api.hip — the core of libsocp's C ABI (include/socp.h): contexts, streams
 // and timing, the problem checks, variant dispatch and the two solver launchers,
-// the batch solves, equilibration and the fused KKT entry.  It defines what
+// the batch solves, equilibration, normalisation and the fused KKT entry.  It defines what
 // socp_host.hpp declares for the other units (socp_api_*.hip); host code only.
 #include <cstdio>
 #include <vector>
 
 #include "socp_equil.hpp"
 #include "socp_host.hpp"
+#include "socp_norm.hpp"
 
 using namespace socp;
 using namespace socp::host;
@@ -109,8 +110,11 @@ extern "C" int socp_ctx_set_equilibration_passes(socp_ctx* c, int passes) {
   return 0;
 }
 
-// SOCP_F_EQUILIBRATE on an entry that does not scale: refused rather than ignored
+// SOCP_F_EQUILIBRATE or SOCP_F_NORMALISE on an entry that does not scale: refused rather than ignored
 int host::check_no_equilibrate(int32_t flags, const char* who) {
+  if (flags & SOCP_F_NORMALISE)
+    return fail(SOCP_E_UNSUPPORTED, std::string(who) + ": SOCP_F_NORMALISE is honoured by socp_batch_solve, "
+                                                       "socp_batch_solve_ex and socp_batch_solve_qp only");
   if (flags & SOCP_F_EQUILIBRATE)
     return fail(SOCP_E_UNSUPPORTED, std::string(who) + ": SOCP_F_EQUILIBRATE is honoured by socp_batch_solve, "
                                                        "socp_batch_solve_ex and socp_batch_solve_qp only");
@@ -404,7 +408,7 @@ extern "C" int socp_debug_exact_fit(const socp_dims* d, const int32_t* kind, con
   // what socp_batch_solve_ex gives launch_small of the choice's inputs
   fill_args(a, *d, d->batch, deg, nullptr);
   a.mode = MODE_SOLVE;
-  a.flags = flags & ~SOCP_F_EQUILIBRATE;
+  a.flags = flags & ~(SOCP_F_EQUILIBRATE | SOCP_F_NORMALISE);
   SmallKernel kern;
   TRY(small_select(v, a, false, &kern));
   for (int pair = SLOT_PAIR_SP; pair <= SLOT_PAIR_PP; ++pair)
@@ -687,6 +691,110 @@ extern "C" int socp_batch_equilibrate(socp_ctx* ctx, const socp_dims* dims, cons
   return 0;
 }
 
+// ------------------------------------------------------- normalisation
+// socp_norm.hip on device pointers.  norm_exponents: the rule's exponents of B
+// problems in the context's B_NX buffer (B x 2 int32, *expo); batchwide: one
+// pair for the whole batch (a shared P), through the norms in B_NN.
+static int norm_exponents(socp_ctx* ctx, int64_t B, int n, int m, int k, const double* cd, const double* bd,
+                          const double* hd, bool batchwide, const int32_t** expo) {
+  typedef socp_ctx X;
+  if (ctx->buf[X::B_NX].ensure((size_t)B * 2 * sizeof(int32_t))) return fail(SOCP_E_NOMEM, "device allocation failed");
+  if (batchwide && ctx->buf[X::B_NN].ensure((size_t)B * 2 * sizeof(unsigned long long)))
+    return fail(SOCP_E_NOMEM, "device allocation failed");
+  NormArgs na;
+  memset(&na, 0, sizeof(na));
+  na.c = cd;
+  na.b = m > 0 ? bd : nullptr;
+  na.h = hd;
+  na.expo = (int32_t*)ctx->buf[X::B_NX].p;
+  na.nrm = batchwide ? (unsigned long long*)ctx->buf[X::B_NN].p : nullptr;
+  na.B = B;
+  na.n = n;
+  na.m = m;
+  na.k = k;
+  HIPCHK(norm_launch(na, ctx->stream));
+  if (batchwide) HIPCHK(norm_batch_launch(na.nrm, na.expo, B, ctx->stream));
+  *expo = na.expo;
+  return 0;
+}
+
+// dst = ldexp(src, +-(sc * ec + sb * eb)) on up to eight arrays of `rows` rows of `len`
+// (row r takes problem r's exponents); NULL and empty arrays are skipped
+struct NormVec {
+  double* dst;
+  const double* src;
+  int64_t len, rows;
+  int sc, sb;
+};
+static int norm_vectors(socp_ctx* ctx, const int32_t* expo, const NormVec* v, int cnt, bool forward) {
+  NormScaleArgs sa;
+  memset(&sa, 0, sizeof(sa));
+  sa.expo = expo;
+  for (int i = 0; i < cnt; ++i) {
+    if (!v[i].dst || !v[i].src || v[i].len == 0 || v[i].rows == 0) continue;
+    NormSeg& s = sa.seg[sa.nseg++];
+    s.dst = v[i].dst;
+    s.src = v[i].src;
+    s.len = v[i].len;
+    s.rows = v[i].rows;
+    s.sc = v[i].sc;
+    s.sb = v[i].sb;
+  }
+  HIPCHK(forward ? norm_forward_launch(sa, ctx->stream) : norm_backward_launch(sa, ctx->stream));
+  return 0;
+}
+
+extern "C" int socp_batch_normalise(socp_ctx* ctx, const socp_dims* dims, const double* Pm, const double* c,
+                                    const double* b, const double* h, int32_t flags, int32_t* expo, double* Ps,
+                                    double* cs, double* bs, double* hs) {
+  if (!ctx) return fail(SOCP_E_INVALID, "ctx is NULL");
+  if (!dims) return fail(SOCP_E_INVALID, "dims is NULL");
+  if (dims->batch < 0 || dims->n <= 0 || dims->m < 0 || dims->k <= 0)
+    return fail(SOCP_E_INVALID, "bad dims (need batch>=0, n>0, m>=0, k>0)");
+  if (dims->batch > kMaxBatch)
+    return fail(SOCP_E_INVALID, "batch above 2^31-1 (problem indices are int32 on the device)");
+  if (flags & ~(SOCP_F_DEVICE_PTRS | SOCP_F_SHARED_MATRICES))
+    return fail(SOCP_E_INVALID, "socp_batch_normalise: flags other than SOCP_F_DEVICE_PTRS | SOCP_F_SHARED_MATRICES");
+  const int64_t B = dims->batch;
+  const int n = dims->n, m = dims->m, k = dims->k;
+  if (B == 0) return 0;
+  if (!c || !h || (m > 0 && !b)) return fail(SOCP_E_INVALID, "NULL data pointer");
+  if (Ps && !Pm) return fail(SOCP_E_INVALID, "a scaled output without its input");
+  HIPCHK(hipSetDevice(ctx->device));
+  const bool dev = (flags & SOCP_F_DEVICE_PTRS) != 0;
+  const bool shared = (flags & SOCP_F_SHARED_MATRICES) != 0;
+  const Stager st{ctx->buf, ctx->stream, dev, nullptr};
+  const size_t MB = shared ? 1 : (size_t)B;
+  typedef socp_ctx X;
+  // host pointers: inputs staged as a solve stages them and scaled in place
+  const double *Pd = nullptr, *cd = nullptr, *bd = nullptr, *hd = nullptr;
+  TRY(st.in(X::B_P, Ps ? Pm : nullptr, MB * n * n, &Pd));
+  TRY(st.in(X::B_C, c, (size_t)B * n, &cd));
+  TRY(st.in(X::B_B, m > 0 ? b : nullptr, (size_t)B * m, &bd));
+  TRY(st.in(X::B_H, h, (size_t)B * k, &hd));
+  double* Psd = !Ps ? nullptr : dev ? Ps : const_cast<double*>(Pd);
+  double* csd = !cs ? nullptr : dev ? cs : const_cast<double*>(cd);
+  double* bsd = !bs ? nullptr : dev ? bs : const_cast<double*>(bd);
+  double* hsd = !hs ? nullptr : dev ? hs : const_cast<double*>(hd);
+  const int32_t* ex = nullptr;
+  TRY(norm_exponents(ctx, B, n, m, k, cd, bd, hd, shared && Pm, &ex));
+  const NormVec fw[4] = {{csd, cd, n, B, 1, 0}, {bsd, bd, m, B, 0, 1}, {hsd, hd, k, B, 0, 1},
+                         {Psd, Pd, (int64_t)n * n, (int64_t)MB, 1, -1}};
+  TRY(norm_vectors(ctx, ex, fw, 4, true));
+  if (expo) {
+    if (dev)
+      HIPCHK(hipMemcpyAsync(expo, ex, (size_t)B * 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    else
+      TRY(st.back(expo, ex, (size_t)B * 2));
+  }
+  TRY(st.back(Ps, Psd, MB * n * n));
+  TRY(st.back(cs, csd, (size_t)B * n));
+  TRY(st.back(bs, bsd, (size_t)B * m));
+  TRY(st.back(hs, hsd, (size_t)B * k));
+  if (!dev) HIPCHK(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
 // socp_batch_solve_ex, and with Pm != NULL socp_batch_solve_qp: the QP solver
 // kernels with the objective x'Px/2 + c'x
 static int batch_solve_impl(socp_ctx* ctx, const socp_dims* dims, const int32_t* cone_kind,
@@ -714,6 +822,11 @@ static int batch_solve_impl(socp_ctx* ctx, const socp_dims* dims, const int32_t*
     return fail(SOCP_E_UNSUPPORTED,
                 "SOCP_F_EQUILIBRATE with SOCP_F_DETECT_INFEASIBLE: the meaning of the infeasibility tolerance would "
                 "move with the scaling");
+  const bool nrm = (P.flags & SOCP_F_NORMALISE) != 0;
+  if (nrm && (P.flags & SOCP_F_DETECT_INFEASIBLE))
+    return fail(SOCP_E_UNSUPPORTED,
+                "SOCP_F_NORMALISE with SOCP_F_DETECT_INFEASIBLE: the meaning of the infeasibility tolerance would "
+                "move with the scaling of c, b and h");
   if (B == 0) return 0;
   if (!c || !G || !h || !x || !z || !s || !iters || !status || (m > 0 && (!A || !b || !y)))
     return fail(SOCP_E_INVALID, "NULL data pointer");
@@ -725,7 +838,7 @@ static int batch_solve_impl(socp_ctx* ctx, const socp_dims* dims, const int32_t*
   const bool warm = (P.flags & SOCP_F_WARM_START) != 0;
   // SOCP_F_SHARED_MATRICES: one A, one G and one sing byte for the whole batch
   const size_t MB = (P.flags & SOCP_F_SHARED_MATRICES) ? 1 : (size_t)B;
-  a.flags = P.flags & ~SOCP_F_EQUILIBRATE;  // (the kernels run what they run without the flag)
+  a.flags = P.flags & ~(SOCP_F_EQUILIBRATE | SOCP_F_NORMALISE);  // (the kernels run what they run without the flags)
   a.mode = MODE_SOLVE;
   if (P.flags & SOCP_F_DETECT_INFEASIBLE) small_set_itol(a, ctx->itol);
   typedef socp_ctx X;
@@ -775,9 +888,48 @@ static int batch_solve_impl(socp_ctx* ctx, const socp_dims* dims, const int32_t*
     a.b = sc[2];
     a.G = sc[3];
     a.h = sc[4];
-    if (qp) small_set_qp(a, sc[5]);
+    if (qp) small_set_qp(a, Pd = sc[5]);
   }
-  TRY(v ? launch_small(ctx, a, v, qp) : launch_large(ctx, a, nullptr, qp));
+  const int32_t* expo = nullptr;
+  if (nrm) {
+    // SOCP_F_NORMALISE: c, b, h and P scaled where they are copies already (staged host data, or
+    // equilibration's), else into context buffers beside the caller's device data; a warm start's
+    // iterate in place
+    double* sc[4] = {const_cast<double*>(a.c), const_cast<double*>(a.b), const_cast<double*>(a.h),
+                     const_cast<double*>(Pd)};
+    if (dev && !eq) {
+      const int slot[4] = {X::B_NC, X::B_NB, X::B_NH, X::B_NP};
+      const size_t cnt[4] = {(size_t)B * n, (size_t)B * m, (size_t)B * k, qp ? MB * n * n : 0};
+      for (int i = 0; i < 4; ++i) {
+        if (cnt[i] == 0) continue;
+        TRY(st.reserve(slot[i], cnt[i] * sizeof(double)));
+        sc[i] = (double*)ctx->buf[slot[i]].p;
+      }
+    }
+    TRY(norm_exponents(ctx, B, n, m, k, a.c, a.b, a.h, qp && MB == 1 && (P.flags & SOCP_F_SHARED_MATRICES), &expo));
+    const NormVec fw[8] = {{sc[0], a.c, n, B, 1, 0},
+                           {sc[1], a.b, m, B, 0, 1},
+                           {sc[2], a.h, k, B, 0, 1},
+                           {sc[3], Pd, (int64_t)n * n, (int64_t)MB, 1, -1},
+                           {warm ? a.x : nullptr, a.x, n, B, 0, 1},
+                           {warm ? a.y : nullptr, a.y, m, B, 1, 0},
+                           {warm ? a.z : nullptr, a.z, k, B, 1, 0},
+                           {warm ? a.s : nullptr, a.s, k, B, 0, 1}};
+    TRY(norm_vectors(ctx, expo, fw, 8, true));
+    a.c = sc[0];
+    a.b = sc[1];
+    a.h = sc[2];
+    if (qp) small_set_qp(a, sc[3]);
+  }
+  const int launched = v ? launch_small(ctx, a, v, qp) : launch_large(ctx, a, nullptr, qp);
+  if (nrm) {
+    // x = 2^-eb x^, y = 2^-ec y^, z = 2^-ec z^, s = 2^-eb s^, whatever the status -- and after a launch that
+    // failed, so that a warm start's iterate in the caller's device buffers does not stay scaled
+    const NormVec bw[4] = {{a.x, a.x, n, B, 0, 1}, {a.y, a.y, m, B, 1, 0}, {a.z, a.z, k, B, 1, 0}, {a.s, a.s, k, B, 0, 1}};
+    const int unscaled = norm_vectors(ctx, expo, bw, 4, false);
+    if (!launched) TRY(unscaled);
+  }
+  TRY(launched);
   if (eq) {  // x = D x^, y = E y^, z = F z^, s = F^-1 s^
     const EquilVec bw[4] = {{a.x, a.x, 0, 1}, {a.y, a.y, 1, 1}, {a.z, a.z, 2, 1}, {a.s, a.s, 2, -1}};
     TRY(equil_vectors(ctx, n, m, k, B, (P.flags & SOCP_F_SHARED_MATRICES) != 0, ex, bw, 4));

@@ -71,11 +71,14 @@ struct socp_ctx {
   int equil_passes = 8;  // SOCP_F_EQUILIBRATE's passes (socp_ctx_set_equilibration_passes)
   // B_EX: the equilibration exponents; B_E*: the scaled copies of device-pointer inputs, and with
   // host pointers the staging of socp_batch_equilibrate's D, E, F
+  // B_NX: SOCP_F_NORMALISE's exponents, B_NN: the norms of its shared-P batch stage; B_N*: the scaled
+  // copies of device-pointer inputs that equilibration has not copied already
   // B_VST: the fused KKT solve's status inside socp_batch_centre / socp_batch_vjp; B_VOUT: the staging of
   // socp_batch_vjp's vector outputs; B_VSUM: socp_batch_vjp_sum's per-slab partial sums
   enum { B_C, B_A, B_B, B_G, B_H, B_SING, B_X, B_Y, B_Z, B_S, B_IT, B_ST, B_RES, B_DX, B_DY,
          B_DZ, B_DS, B_CX, B_CY, B_CZ, B_CS, B_CNT, B_LWS, B_ERR, B_P, B_EX, B_EC, B_EA, B_EB,
-         B_EG, B_EH, B_EP, B_VST, B_VOUT, B_VSUM, NB };
+         B_EG, B_EH, B_EP, B_VST, B_VOUT, B_VSUM, B_NX, B_NN,
+         B_NC, B_NB, B_NH, B_NP, NB };
   socp::host::DevBuf buf[NB];
 };
 
@@ -136,6 +139,7 @@ void handle_free(H* h) {
 int check_problem(const socp_dims* d, const int32_t* kind, const int32_t* offs, const int32_t* dim, ConeTable* tab,
                   int* degree);
 int check_detect_flags(int32_t flags);
+// SOCP_F_EQUILIBRATE or SOCP_F_NORMALISE on an entry that does not scale
 int check_no_equilibrate(int32_t flags, const char* who);
 int check_qp_flags(int32_t flags, const char* who);
 extern const char* const kUnsupported;

@@ -32,6 +32,7 @@ const SOCP_F_DETECT_INFEASIBLE = Int32(256)
 # batches); the outputs are bitwise those of the replicated call (include/socp.h)
 const SOCP_F_SHARED_MATRICES = Int32(512)
 const SOCP_F_EQUILIBRATE = Int32(1024)
+const SOCP_F_NORMALISE = Int32(2048)
 const SOCP_PRIMAL_INFEASIBLE = Int32(5)
 const SOCP_DUAL_INFEASIBLE = Int32(6)
 "tau of the detection rule for every later solve of this process's context (default 1e-7)."
@@ -292,11 +293,15 @@ parametric batch) every problem's `A`, `G` and `sing` must equal the first's
 (`SOCP_F_SHARED_MATRICES`).  With `equilibrate=true` (`SOCP_F_EQUILIBRATE`) the
 problems are scaled on the device by power-of-two Ruiz factors, solved and
 unscaled exactly; `tol` then refers to the scaled problem and `sing` is probed
-on the scaled `G`.  Not together with `detect_infeasible`.
+on the scaled `G`.  Not together with `detect_infeasible`.  With
+`normalise=true` (`SOCP_F_NORMALISE`) `c` and `(b, h)` of every problem are
+scaled by one power of two each so that their largest entries lie in [1, 2),
+the problem is solved and the iterates are unscaled exactly; `tol` then refers
+to the normalised problem.  Not together with `detect_infeasible` either.
 """
 function solve_socp_batched(problems::AbstractVector{<:Problem}; maxit=40, tol=1e-5, explicit_inverse::Bool=false,
                             detect_infeasible::Bool=false, shared_matrices::Bool=false,
-                            equilibrate::Bool=false)
+                            equilibrate::Bool=false, normalise::Bool=false)
     p0 = problems[1]
     n, m, k = p0.n, p0.m, p0.k
     B = length(problems)
@@ -313,7 +318,8 @@ function solve_socp_batched(problems::AbstractVector{<:Problem}; maxit=40, tol=1
     flags = (explicit_inverse ? SOCP_F_EXPLICIT_INVERSE : Int32(0)) |
             (detect_infeasible ? SOCP_F_DETECT_INFEASIBLE : Int32(0)) |
             (shared_matrices ? SOCP_F_SHARED_MATRICES : Int32(0)) |
-            (equilibrate ? SOCP_F_EQUILIBRATE : Int32(0))
+            (equilibrate ? SOCP_F_EQUILIBRATE : Int32(0)) |
+            (normalise ? SOCP_F_NORMALISE : Int32(0))
     params = Ref(SocpParams(maxit, 3, tol, 0.99, 1e-10, flags, 0))
     dims = Ref(SocpDims(B, n, m, k, length(p0.cones)))
     rc = ccall((:socp_batch_solve, libsocp), Cint,

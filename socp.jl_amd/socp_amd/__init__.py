@@ -22,7 +22,7 @@ import numpy as np
 from . import _lib
 from ._lib import (CHOL_H_FAILED, CHOL_S_FAILED, CONE_POC, CONE_SOC, CONVERGED, DOMAIN_ERROR, DUAL_INFEASIBLE,
                    F_DETECT_INFEASIBLE, F_DEVICE_PTRS, F_EQUILIBRATE, F_EXPLICIT_INVERSE, F_FORCE_LARGE,
-                   F_SHARED_MATRICES,
+                   F_NORMALISE, F_SHARED_MATRICES,
                    F_WARM_START, MAXIT,
                    PRIMAL_INFEASIBLE, Context, SocpError,
                    default_context,
@@ -32,7 +32,7 @@ __all__ = [
     "POC", "SOC", "Problem", "State", "Scaling", "DenseSolver", "HipDenseSolver", "SolverState",
     "solve_socp", "solve_socp_batched", "compute_scaling", "setup_iter", "solve_kkt",
     "PosDefException", "DomainError", "batch_solve", "batch_kkt_solve", "DenseHandle", "Ingest",
-    "generate", "pack_csc", "equilibrate", "batch_centre", "batch_vjp",
+    "generate", "pack_csc", "equilibrate", "normalise", "batch_centre", "batch_vjp",
     "Context", "SocpError", "default_context", "cone_arrays",
     "CONVERGED", "MAXIT", "CHOL_H_FAILED", "CHOL_S_FAILED", "DOMAIN_ERROR",
     "PRIMAL_INFEASIBLE", "DUAL_INFEASIBLE",
@@ -181,7 +181,7 @@ def _check_P(P, G, MB, n):
 def batch_solve(cones, n, m, k, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5, step=0.99,
                 sigma_exp=3, init_eps=1e-10, warm=None, ctx=None, res=False, out=None, force_large=False,
                 explicit_inverse=False, detect_infeasible=False, shared_matrices=False, P=None,
-                equilibrate=False):
+                equilibrate=False, normalise=False):
     """Solve a batch of independent problems (same dims and cone structure).
 
     Arrays follow include/socp.h: per-problem column-major A (m x n), G (k x n)
@@ -216,6 +216,13 @@ def batch_solve(cones, n, m, k, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5,
     sing=None probe and res then refer to the scaled problem; the inputs are
     not written.  Not together with warm or detect_infeasible
     (SOCP_E_UNSUPPORTED).
+    normalise (SOCP_F_NORMALISE): scale c by one power of two per problem and
+    (b, h) by another (``normalise``'s rule: their largest entries come to lie
+    in [1, 2)), solve, and unscale exactly -- the outputs are bitwise those of
+    that three-step pipeline.  tol, init_eps and res then refer to the
+    normalised problem, so the exit test is relative to the sizes of c and of
+    (b, h); the inputs are not written.  Not together with detect_infeasible
+    (SOCP_E_UNSUPPORTED).
     Returns dict(x, y, z, s, iters, status[, res]).
     """
     L = _lib.load()
@@ -247,6 +254,8 @@ def batch_solve(cones, n, m, k, c, A, b, G, h, sing=None, *, maxit=40, tol=1e-5,
         flags |= F_SHARED_MATRICES
     if equilibrate:
         flags |= F_EQUILIBRATE
+    if normalise:
+        flags |= F_NORMALISE
     pr = default_params(maxit=maxit, tol=tol, step=step, sigma_exp=sigma_exp, init_eps=init_eps,
                         flags=flags)
     if dev:
@@ -347,6 +356,54 @@ def equilibrate(cones, n, m, k, A, G, P=None, c=None, b=None, h=None, *, shared_
     _lib.check(L.socp_batch_equilibrate(
         ctx.handle, dims, p(kind), p(offs), p(dim), p(ins["P"]), p(ins["c"]), p(ins["A"]), p(ins["b"]), p(ins["G"]),
         p(ins["h"]), flags, po("D"), po("E"), po("F"), po("Ps"), po("cs"), po("As"), po("bs"), po("Gs"), po("hs")))
+    return out
+
+
+def normalise(n, m, k, c, b, h, P=None, *, shared_matrices=False, ctx=None):
+    """SOCP_F_NORMALISE's rule on the device (socp_batch_normalise; the rule is
+    in include/socp.h).  c (n), b (m; None when m = 0) and h (k) are stacked
+    batch-major; P (n x n, optional) is column-major, ONE matrix with
+    shared_matrices, and then the whole batch takes one pair of exponents.
+    numpy inputs go through host staging and the call synchronises; torch CUDA
+    tensors are used in place, stream-ordered.  The inputs are not written.
+    Returns a dict with expo (2 x batch int32: ec, eb per problem),
+    cs = ldexp(c, ec), bs = ldexp(b, eb), hs = ldexp(h, eb) and, with a P,
+    Ps = ldexp(P, ec - eb)."""
+    L = _lib.load()
+    B = _size(c) // n
+    if B * n != _size(c):
+        raise ValueError(f"c: {_size(c)} elements is not a multiple of n={n}")
+    MB = 1 if shared_matrices else B
+    _check_sizes(B, b=(b if m else None, B * m), h=(h, B * k), P=(P, MB * n * n))
+    dev = _is_torch(c)
+    ctx = ctx or default_context()
+    ins = dict(P=P, c=c, b=b if m else None, h=h)
+    if dev:
+        import torch
+        ctx.bind_torch_stream()
+        new = lambda cnt, dt=torch.float64: torch.empty(max(cnt, 1), dtype=dt, device=c.device)[:cnt]  # noqa: E731
+        i32 = torch.int32
+        for key, v in ins.items():
+            if v is not None and (not _is_torch(v) or str(v.dtype) != "torch.float64" or v.device != c.device
+                                  or not v.is_contiguous()):
+                raise ValueError(f"{key} must be a contiguous float64 tensor on c's device")
+    else:
+        new = lambda cnt, dt=np.float64: np.zeros(cnt, dt)  # noqa: E731
+        i32 = np.int32
+        ins = {key: _host(v) for key, v in ins.items()}
+    out = dict(expo=new(2 * B, i32))
+    for key, v in ins.items():
+        if v is not None:
+            out[key + "s"] = new(_size(v))
+    p = _lib.ptr
+    dims = _lib.Dims(B, n, m, k, 0)
+    flags = (F_DEVICE_PTRS if dev else 0) | (F_SHARED_MATRICES if shared_matrices else 0)
+
+    def po(key):  # NULL for an absent or empty array
+        v = out.get(key)
+        return p(v) if v is not None and _size(v) else None
+    _lib.check(L.socp_batch_normalise(ctx.handle, dims, p(ins["P"]), p(ins["c"]), p(ins["b"]), p(ins["h"]), flags,
+                                      po("expo"), po("Ps"), po("cs"), po("bs"), po("hs")))
     return out
 
 
@@ -1190,23 +1247,27 @@ class SolverState:
         self.iters, self.status = 0, None
 
 
-def solve_socp(prob: Problem, ss: SolverState) -> State:
+def solve_socp(prob: Problem, ss: SolverState, *, normalise=False) -> State:
     """solve_socp(prob, ss) (solver.jl:40-153) on the GPU.  Like the reference it
-    returns the final State, and raises where the reference throws."""
+    returns the final State, and raises where the reference throws.  normalise
+    as in ``batch_solve`` (dense solver only)."""
+    if normalise and isinstance(ss.solver, SparseSolver):
+        raise ValueError("normalise: the rank-update solver does not scale (SOCP_E_UNSUPPORTED)")
     if isinstance(ss.solver, SparseSolver):  # the rank-update plugin's own IPM (spsolver.jl)
         out = ss.solver.handle.solve_socp(prob.c, prob.b if prob.m else None, prob.h, maxit=ss.maxit, tol=ss.tol)
     else:
         out = batch_solve(prob.cones, prob.n, prob.m, prob.k, prob.c, _colmajor(prob.A, prob.m, prob.n),
                           prob.b, _colmajor(prob.G, prob.k, prob.n), prob.h,
                           np.array([prob.sing], np.uint8), maxit=ss.maxit, tol=ss.tol,
-                          ctx=ss.solver.ctx, P=None if prob.P is None else _colmajor(prob.P, prob.n, prob.n))
+                          ctx=ss.solver.ctx, P=None if prob.P is None else _colmajor(prob.P, prob.n, prob.n),
+                          normalise=normalise)
     ss.iters, ss.status = int(out["iters"][0]), int(out["status"][0])
     _raise_status(ss.status)
     return State(prob, out["x"], out["y"], out["z"], out["s"])
 
 
 def solve_socp_batched(problems, maxit=40, tol=1e-5, ctx=None, solver="dense", detect_infeasible=False,
-                       shared_matrices=False, equilibrate=False):
+                       shared_matrices=False, equilibrate=False, normalise=False):
     """Batched solve of Problems sharing dims and cones; returns (states, iters, status)
     without raising: failures are reported per problem.  solver="dense": the
     DenseSolver path (the fused register / blocked kernels); "sqr": the
@@ -1218,7 +1279,8 @@ def solve_socp_batched(problems, maxit=40, tol=1e-5, ctx=None, solver="dense", d
     When any problem carries a P the batch runs the QP entry (``batch_solve``'s
     P; dense solver only); problems without one get zeros, and with
     shared_matrices every P must equal the first's as well.  equilibrate as in
-    ``batch_solve`` (dense solver only); `sing` is then probed on the scaled G."""
+    ``batch_solve`` (dense solver only); `sing` is then probed on the scaled G.
+    normalise as in ``batch_solve`` (dense solver only)."""
     p0 = problems[0]
     n, m, k = p0.n, p0.m, p0.k
     for p in problems:
@@ -1247,6 +1309,8 @@ def solve_socp_batched(problems, maxit=40, tol=1e-5, ctx=None, solver="dense", d
         P = np.concatenate([_colmajor(p.P, n, n) if p.P is not None else np.zeros(n * n) for p in mats])
     if equilibrate and solver == "sqr":
         raise ValueError("equilibrate: the rank-update solver does not scale (SOCP_E_UNSUPPORTED)")
+    if normalise and solver == "sqr":
+        raise ValueError("normalise: the rank-update solver does not scale (SOCP_E_UNSUPPORTED)")
     if solver == "sqr":
         out = SqrHandle(p0.cones, n, m, k, A, G, sing, ctx=ctx, shared_matrices=shared_matrices,
                         batch=len(problems)).solve_socp(
@@ -1254,7 +1318,7 @@ def solve_socp_batched(problems, maxit=40, tol=1e-5, ctx=None, solver="dense", d
     else:
         out = batch_solve(p0.cones, n, m, k, c, A, b, G, h, None if equilibrate else sing, maxit=maxit, tol=tol,
                           ctx=ctx, detect_infeasible=detect_infeasible, shared_matrices=shared_matrices, P=P,
-                          equilibrate=equilibrate)
+                          equilibrate=equilibrate, normalise=normalise)
     states = [State(p, out["x"][i * n:(i + 1) * n], out["y"][i * m:(i + 1) * m],
                     out["z"][i * k:(i + 1) * k], out["s"][i * k:(i + 1) * k])
               for i, p in enumerate(problems)]

@@ -23,6 +23,7 @@ F_DEVICE_PTRS, F_WARM_START, F_FORCE_LARGE, F_EXPLICIT_INVERSE = 1, 2, 4, 8
 F_DETECT_INFEASIBLE = 256  # bits 16..128 are the CPU oracle's
 F_SHARED_MATRICES = 512  # one A, G, sing for the whole batch (SOCP_F_SHARED_MATRICES)
 F_EQUILIBRATE = 1024  # power-of-two Ruiz scaling before the solve, exact unscaling after (SOCP_F_EQUILIBRATE)
+F_NORMALISE = 2048  # power-of-two scaling of c and of (b, h) before the solve, exact unscaling after (SOCP_F_NORMALISE)
 
 EXPORTED = [
     "socp_last_error", "socp_version", "socp_params_default", "socp_ctx_create",
@@ -44,6 +45,7 @@ EXPORTED = [
     "socp_ingest_submit_qp", "socp_ingest_set_matrices_qp",
     "socp_batch_centre", "socp_batch_vjp",
     "socp_batch_vjp_sum", "socp_debug_vjp_sum_plan",
+    "socp_batch_normalise",
 ]
 # declared and exported as well, but kept out of the list above: tests/test_abi.py compares that
 # list with the header's lower-case names
@@ -114,6 +116,8 @@ def load():
         L.socp_ctx_set_equilibration_passes.argtypes = [vp, C.c_int]
         L.socp_batch_equilibrate.argtypes = ([vp, C.POINTER(Dims), i32p, i32p, i32p] + [dp] * 6 + [C.c_int32]
                                              + [dp] * 9)
+    if hasattr(L, "socp_batch_normalise"):  # normalisation (absent from older A/B builds)
+        L.socp_batch_normalise.argtypes = [vp, C.POINTER(Dims)] + [dp] * 4 + [C.c_int32, i32p] + [dp] * 4
     L.socp_supported.argtypes = [C.POINTER(Dims)]
     if hasattr(L, "socp_debug_slot_plan"):  # (absent from older A/B builds)
         L.socp_debug_slot_plan.argtypes = [C.POINTER(Dims), i32p, i32p, i32p] + [C.POINTER(C.c_int32)] * 3

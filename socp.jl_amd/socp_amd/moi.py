@@ -154,7 +154,7 @@ class ModelData:
 class Optimizer:
     """`Socp.Optimizer` (moi.jl:57-66) over the GPU dense path.  Keyword options:
     `maxit` (default 40, solver.jl:105), `tol` (1e-5, solver.jl:122), `ctx`,
-    `equilibrate` (default False; `optimize_batched`)."""
+    `equilibrate` and `normalise` (default False; `optimize_batched`)."""
 
     def __init__(self, **options):
         self.options = dict(options)
@@ -347,6 +347,9 @@ def optimize_batched(optimizers, ctx=None, shared_matrices=False):
     then refers to the scaled problem, and `sing` is probed on the scaled G).
     The library refuses detection together with that flag, so these groups run
     without it: an infeasible model ends with a numerical status, not a certificate.
+    Models built with `Optimizer(normalise=True)` group apart in the same way and
+    are solved with SOCP_F_NORMALISE (``batch_solve``'s normalise: `tol` then
+    refers to the normalised problem), likewise without detection.
     Models with a quadratic objective (ScalarQuadraticFunction) form groups of
     their own as well and run ``batch_solve(P=...)`` (socp_batch_solve_qp), for
     the same reason without detection: the library refuses that pair too.  With
@@ -355,11 +358,12 @@ def optimize_batched(optimizers, ctx=None, shared_matrices=False):
     for o in optimizers:
         d = o.build()
         key = d.signature + (int(o.options.get("maxit", 40)), float(o.options.get("tol", 1e-5)),
-                             bool(o.options.get("equilibrate", False)), d.P is not None)
+                             bool(o.options.get("equilibrate", False)), d.P is not None,
+                             bool(o.options.get("normalise", False)))
         groups.setdefault(key, []).append(o)
     for key, opts in groups.items():
         n, f, l, qa = key[:4]
-        maxit, tol, equil, quad = key[4], key[5], key[6], key[7]
+        maxit, tol, equil, quad, norm = key[4], key[5], key[6], key[7], key[8]
         k = l + sum(qa)
         ds = [o.data for o in opts]
         if shared_matrices:
@@ -377,8 +381,8 @@ def optimize_batched(optimizers, ctx=None, shared_matrices=False):
         h = np.concatenate([d.h for d in ds])
         P = np.concatenate([d.P.ravel(order="F") for d in ms]) if quad else None
         out = batch_solve(ds[0].cones, n, f, k, c, A, b, G, h, sing, maxit=maxit, tol=tol,
-                          detect_infeasible=not (equil or quad), equilibrate=equil, shared_matrices=shared_matrices,
-                          P=P,
+                          detect_infeasible=not (equil or quad or norm), equilibrate=equil, normalise=norm,
+                          shared_matrices=shared_matrices, P=P,
                           ctx=ctx if ctx is not None else opts[0].options.get("ctx"))
         for i, o in enumerate(opts):
             o._set_solution(out["x"][i * n:(i + 1) * n], out["y"][i * f:(i + 1) * f],

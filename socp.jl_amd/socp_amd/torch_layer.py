@@ -99,21 +99,26 @@ class SocpFunction(torch.autograd.Function):
 
 
 class SocpLayer(torch.nn.Module):
-    """``SocpLayer(cones, n, m, k, *, centre_steps=4, shared_matrices=False, **solve_options)``
+    """``SocpLayer(cones, n, m, k, *, centre_steps=4, shared_matrices=False, normalise=False, **solve_options)``
 
     cones: ``batch_solve``'s cone table.  centre_steps: the Newton centring
     steps after the solve (0: differentiate at the solver's iterate, which is
     wrong by the iterate's distance from the central path).  shared_matrices:
     one A, G (and P, sing) for the batch -- the parametric case; c, b and h get
-    per-problem gradients, A, G and P the batch's sum.  solve_options go to
-    ``batch_solve`` (maxit, tol, force_large, ctx, ...).
+    per-problem gradients, A, G and P the batch's sum.  normalise:
+    ``batch_solve``'s (SOCP_F_NORMALISE), for the forward solve only -- the
+    centring and the adjoint work on the caller's data, and the un-normalised
+    iterate is what they receive.  solve_options go to ``batch_solve`` (maxit,
+    tol, force_large, ctx, ...).
 
     ``layer(c, A, b, G, h, P=None, sing=None)`` returns
     ``(x, y, z, s, status, iters)``; see ``SocpFunction`` and the module
     docstring for the layout: G is a ``(B, n, k)`` tensor of columns."""
 
-    def __init__(self, cones, n, m, k, *, centre_steps=4, shared_matrices=False, **solve_options):
+    def __init__(self, cones, n, m, k, *, centre_steps=4, shared_matrices=False, normalise=False, **solve_options):
         super().__init__()
+        if normalise:
+            solve_options["normalise"] = True
         self.cfg = _Config(cones, n, m, k, centre_steps, shared_matrices, solve_options)
 
     def forward(self, c, A, b, G, h, P=None, sing=None):
